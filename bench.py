@@ -14,14 +14,22 @@ all-gather of the result (csrc/nadm_step.hip, NADM_MODE_DP) -- every step is ONE
                      100 rows/GPU at N=8 for the default B=800; "strong": the work per step is fixed)
 
     python bench.py --gpus 1 --steps 100 --warmup 30
-    python bench.py --gpus 8                       # spawns 8 ranks itself (re-exec under torch.distributed.run)
+    python bench.py --gpus 1 --steps 100 --warmup 30 --full    # + kernel table, roofline, box fingerprint, epoch loop, CPU baselines
+    python bench.py --gpus 8 --full                # spawns 8 ranks itself (a child process under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --min-k 2 --max-k 10 --rows 2504 --snps 600000      # configs[2]: nine heads over one pass of X
 
-With N > 1 ranks the same processes go on, behind the headline, to time every open multi-GPU alternative (`"alt"` in the JSON line:
-the reference's global batch 800, SNP sharding at both batch semantics, message B in two buckets, a second communicator for message
-A) and the step's own collectives at their real sizes (`"collectives"`), so that ONE run on an 8-GPU node decides DESIGN.md section 5's
-open questions.  `--alt` runs those legs on one GPU too; `--share-gpu` proves the whole flow on a one-GPU box.
+A plain run does what the headline needs and nothing else: set-up, the clock ramp and the warm-up steps, the --steps timed steps,
+the outputs of the last timed step if --dump-outputs is given, and the JSON line.  Everything else it measures runs only with --full:
+the per-kernel table and the roofline of the dominant kernel, the kernel's own clock, the host's queueing cost, the box fingerprint,
+the production epoch loop, the CPU baselines, and with N > 1 ranks (or --alt) every open multi-GPU alternative behind the headline
+(`"alt"` in the JSON line: the reference's global batch 800, SNP sharding at both batch semantics, message B in two buckets, a second
+communicator for message A) and the step's own collectives at their real sizes (`"collectives"`), so that ONE run on an 8-GPU node
+decides DESIGN.md section 5's open questions.  `--share-gpu` proves the whole flow on a one-GPU box.
+
+The clock ramp runs for a wall-clock time, so its number of steps varies from run to run; the parameters and the optimizer state go
+back to their start behind it, so that with the same arguments the warm-up and timed steps see the same inputs in every run and
+--dump-outputs writes the same arrays for the same build.
 """
 import argparse
 import hashlib
@@ -41,6 +49,7 @@ HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 
 MFMA_BF16_PEAK_TFLOPS = 2500.0   # dense bf16 matrix peak (same guide); the three GEMM-shaped products run as bf16 pieces
 N_SIMD = 256 * 4          # 256 CUs x 4 SIMDs
 PROFILE_ROUND = "r06"     # profiles/<round>_pmc_*.json hold the counter passes of the kernels of THIS build (tools/pmc_profile.py)
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this many bytes of arrays
 
 import contextlib
 
@@ -91,13 +100,14 @@ def parse():
                     help="single GPU, with --force-ddp: the step of rank 0 of W ranks with no-op collectives (nadm_comm_emulated) -- Adam on 1/W of "
                          "the parameters, the rest treated as gathered.  The per-rank GPU and host cost of a W-rank step; NOT a scaling measurement")
     ap.add_argument("--time-kernels", choices=("dominant", "all"), default="dominant",
-                    help="HIP events inside the timed region around the dominant kernel only (default: two event records per step) "
+                    help="with --full: HIP events inside the timed region around the dominant kernel only (default: two event records per step) "
                          "or around every kernel of the step (kernel_ms table; the records cost ~4 %% of the step)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="functional check of the N>1 flow on a ONE-GPU box: all ranks use cuda:0 and gloo carries the tensors "
                          "(RCCL refuses two ranks per device); not a measurement")
-    ap.add_argument("--alt", action="store_true", help="run the alternative multi-GPU legs + the collective micro-benchmark behind the headline (default at N > 1)")
-    ap.add_argument("--no-alt", action="store_true", help="N > 1: only the headline")
+    ap.add_argument("--alt", action="store_true", help="with --full: run the alternative multi-GPU legs + the collective micro-benchmark behind the "
+                                                      "headline on one GPU too (default at N > 1)")
+    ap.add_argument("--no-alt", action="store_true", help="N > 1 with --full: no alternative legs")
     ap.add_argument("--alt-steps", type=int, default=50, help="timed steps of every alternative leg")
     ap.add_argument("--alt-warmup", type=int, default=10, help="untimed steps in front of every alternative leg")
     ap.add_argument("--alt-deadline", type=float, default=420.0,
@@ -109,11 +119,20 @@ def parse():
     ap.add_argument("--no-epoch-loop", action="store_true", help="skip the production epoch loop behind the timed region (profiling passes: only the K-step kernels)")
     ap.add_argument("--cpu-rows", type=int, default=2400, help="rows of the same workload used for the bounded CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=12, help="timed steps of the CPU baseline (min / median / max reported)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything behind the headline: kernel table, roofline, clock probe, host queueing cost, box fingerprint, epoch loop, "
+                         "CPU baselines and, with several ranks, the alternative legs and collectives (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left to its caller as DIR/<name>.npy: V, every head's P, the MLP weights and the "
+                         "loss value (rank 0; a fixed seeded sample of the SNPs where V and P exceed %d MB)" % (DUMP_BYTES // 10**6))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
-    """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one process per GPU."""
+    """`python bench.py --gpus N` without a launcher: torch.distributed.run in a child process, one rank per GPU; exits with its status."""
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -122,7 +141,8 @@ def spawn_ranks(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(cmd[0], cmd, env)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def source_hash():
@@ -354,21 +374,23 @@ def collectives_bench(comm, lay, dev, world, reps=20):
 
 
 def validate_line(d, world):
-    """Problems (strings) with a bench JSON line as the driver / a reader needs it; empty = fine.  With several ranks (or --alt) every
-    alternative leg and every collective of the micro-benchmark must be there with a positive time."""
+    """Problems (strings) with a bench JSON line as the driver / a reader needs it; empty = fine.  A --full line carries the roofline and
+    the box fingerprint, and with several ranks (or --alt) every alternative leg and every collective of the micro-benchmark with a
+    positive time."""
     bad = []
+    full = d.get("full", True)                                          # (lines from before the option: all were full)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
-              "data", "config", "roofline", "box"):
+              "data", "config") + (("roofline", "box") if full else ()):
         if k not in d:
             bad.append(f"missing {k}")
     if d.get("n_gpus") != world:
         bad.append(f"n_gpus {d.get('n_gpus')} != {world}")
     if not (isinstance(d.get("value"), (int, float)) and d["value"] > 0 and d.get("ms_per_step", 0) > 0):
         bad.append("value / ms_per_step not positive")
-    for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
+    for k in ("bound", "achieved", "peak", "unit", "frac", "traffic") if full else ():
         if k not in (d.get("roofline") or {}):
             bad.append(f"roofline.{k} missing")
-    if world > 1 or "alt" in d:
+    if (world > 1 and full) or "alt" in d:
         alt, coll = d.get("alt") or {}, d.get("collectives") or {}
         for leg in ALT_LEGS:
             v = alt.get(leg)
@@ -379,6 +401,31 @@ def validate_line(d, world):
             if not v or not (v.get("us", 0) > 0 and v.get("bytes", 0) > 0 and "bus_gbs" in v):
                 bad.append(f"collectives.{c} missing or empty")
     return bad
+
+
+def dump_outputs(eng, loss_last, out_dir):
+    """--dump-outputs: what the timed path leaves its caller after its last step, as float32 / float64 .npy files -- V [M, C], P_k<K>
+    [M, K] per head, the MLP weights g, W1, b1, Wk_k<K>, bk_k<K>, and the loss value of that step (float64, absent with --no-loss).
+    Where V and the P would exceed DUMP_BYTES, the same fixed seeded sample of SNP rows (in ascending order) is taken from every one."""
+    L, h = eng.lay, eng.lay.heads
+    sm = eng.small.cpu().numpy()
+    arrays = {"g": sm[h.g_off:h.g_off + L.C], "W1": sm[h.w1_off:h.w1_off + L.Hd * L.C].reshape(L.Hd, L.C), "b1": sm[h.b1_off:h.b1_off + L.Hd]}
+    for i, k in enumerate(L.ks):
+        arrays[f"Wk_k{k}"] = sm[h.wk_off[i]:h.wk_off[i] + k * L.Hd].reshape(k, L.Hd)
+        arrays[f"bk_k{k}"] = sm[h.bk_off[i]:h.bk_off[i] + k]
+    keep = (DUMP_BYTES - 4 * sm.size - 4096) // (4 * (L.C + sum(L.ks)))
+    rows = None
+    if keep < eng.M:
+        rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(eng.M, keep, replace=False))).to(eng.device)
+    take = lambda t: (t if rows is None else t.index_select(0, rows)).float().cpu().numpy()
+    arrays["V"] = take(eng.V())
+    for i, k in enumerate(L.ks):
+        arrays[f"P_k{k}"] = take(eng.P(i))
+    if loss_last is not None:
+        arrays["loss"] = np.array([loss_last], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def bench_params(M, S):
@@ -562,8 +609,8 @@ def main():
                         n_buckets=n_buckets if ddp else 1, comm_a=comm_a, p3_whole=args.p3_whole)
         eng.set_packed(make_dataset(eng, rows_local, rank * rows_local, K, dev))
         gperm = torch.Generator(device="cpu").manual_seed(1000 + rank)
-    eng.load_params(V0, P0, init_encoder_weights(42, 8, args.hidden, ks))
-    del V0, P0
+    small0 = init_encoder_weights(42, 8, args.hidden, ks)
+    eng.load_params(V0, P0, small0)
     if world > 1 and not snp:
         # the production trainer stores a rank's rows in shard order and steps through them contiguously (model.py launch_training:
         # `order = seq`; DistributedSampler.set_epoch is never called, src/loaders.py:27): the bench's pass 1 gathers what the trainer's does
@@ -593,16 +640,21 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             if float(t.item()) == 0.0:
                 break
+    # how many steps the ramp took depends on the clock: back to the start, so that what follows computes the same in every run
+    eng.load_params(V0, P0, small0)
+    eng.read_loss(reset=True)
+    del V0, P0
     for s in range(args.warmup):
-        step(n_ramp + s)
+        step(s)
     from neural_admixture_amd._lib import T_NAMES
-    eng.time_kernels(T_NAMES if args.time_kernels == "all" else ("decode_bce",))
+    if args.full:
+        eng.time_kernels(T_NAMES if args.time_kernels == "all" else ("decode_bce",))
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s in range(args.steps):
-        step(n_ramp + args.warmup + s)
+        step(args.warmup + s)
     eng.sync()                                             # what the last step left to "the next one" belongs to the timed work
     t_queued = time.perf_counter() - t0                    # the host has queued everything (the GPU is still running)
     if world > 1:
@@ -614,15 +666,69 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    kms = eng.kernel_ms()
     loss_sum, loss_last = eng.read_loss()
     assert np.isfinite(loss_last) or not with_loss
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, loss_last if with_loss else None, args.dump_outputs)
+    per_step_units = (gb if snp else b * world) * M
+    cfg_name = {(100_000, 500_000, (8,)): "configs[3]", (500_000, 1_000_000, (16,)): "configs[4]", (2504, 600_000, (7,)): "configs[1]",
+                (2504, 600_000, tuple(range(2, 11))): "configs[2]"}.get((args.rows, M, tuple(ks)), "configs[3] shape, resized")
+    mode = "snp" if snp else ("dp-global-batch" if args.global_batch is not None else "dp")
+    out = {
+        "metric": "genotypes/sec (samples x SNPs / epoch-sec) at K=%s" % (K if len(ks) == 1 else f"{ks[0]}..{ks[-1]}"),
+        "value": per_step_units * args.steps / dt, "unit": "genotypes/s",
+        "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong" if args.global_batch is not None else "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
+        "config": {"workload": f"{cfg_name}: synthetic {args.rows} samples x {M} SNPs, K={'/'.join(map(str, ks))}, 2-bit packed resident in HBM, "
+                               f"{'SNP' if snp else 'sample'}-sharded over {world} GPU(s), batch {b}/GPU, hidden {args.hidden}, n_components 8, "
+                               f"loss value {'every step' if with_loss else 'skipped'}",
+                   "global_batch": gb if snp else b * world, "parallelism": f"{args.parallelism}{world}", "mode": mode,
+                   "clock_ramp_steps_untimed": n_ramp, "transport": comm.kind if comm is not None else None,
+                   "emulated_world": args.emulate_world,
+                   "message_b_buckets": eng.lay.n_buckets if ddp else None, "pass3_in_ranges": (not args.p3_whole) if ddp else None,
+                   "second_communicator": (eng.comm_a is not None) if ddp else None},
+        # the timed region's own loop took t_queued to queue (GPU-bound: the launch queue stays ahead)
+        "host_loop_ms_per_step_in_timed_region": t_queued / args.steps * 1e3,
+        "loss_last_step": loss_last,
+    }
+    if world > 1:
+        out["ms_per_step_this_rank"] = dt_rank / args.steps * 1e3          # rank 0's own clock; ms_per_step is the max over ranks
+    if args.share_gpu:
+        out["config"]["share_gpu"] = "all ranks on cuda:0 over gloo: functional check, not a measurement"
+    if args.full:
+        full_measurements(args, out, eng, comm, dev, world, rank, ks, b, gb, M, S, snp, ddp, rows_local, with_loss, lr, step, dt)
+    if rank == 0:
+        problems = validate_line(out, world)
+        if problems:
+            print(f"[bench] incomplete line: {problems}", file=sys.stderr)
+        print(json.dumps(out))
+        sys.stdout.flush()
+    if hang_guard is not None:
+        hang_guard.cancel()
+    comm_a2 = eng.comm_a
+    if comm is not None:                                                # every rank gets here: the communicator goes down together
+        del eng
+        comm.close()
+        if comm_a2 is not None:
+            comm_a2.close()
+    if use_dist:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, out, eng, comm, dev, world, rank, ks, b, gb, M, S, snp, ddp, rows_local, with_loss, lr, step, dt):
+    """--full: everything behind the headline, after the timed steps and in the same process (adds its figures to `out`)."""
+    from neural_admixture_amd._lib import T_NAMES
+    if world > 1:
+        import torch.distributed as dist
+    kms = eng.kernel_ms()
+    s_next = args.warmup + args.steps                                   # the batches behind the timed ones
     if args.time_kernels == "dominant":
         # the other kernels of the step, for the kernel_ms table only: a short pass AFTER the timed region with events around
         # every kernel (those records cost ~4 % of the step, which is why the timed region carries only the dominant kernel's)
         eng.time_kernels(T_NAMES)
         for s in range(min(args.steps, 20)):
-            step(n_ramp + args.warmup + args.steps + s)
+            step(s_next + s)
         eng.sync()
         torch.cuda.synchronize()
         for name, v in eng.kernel_ms().items():
@@ -637,7 +743,7 @@ def main():
     if not args.no_clock_probe:
         _nlib.nadm_clock_probe(_ptr(clk_probe))
         for s in range(20):
-            step(n_ramp + args.warmup + args.steps + 20 + s)
+            step(s_next + 20 + s)
         eng.sync()
         torch.cuda.synchronize()
         _nlib.nadm_clock_probe(None)
@@ -739,63 +845,38 @@ def main():
                  "note": "instruction counts and busy fractions: replayed counter passes (issue_source); clock and launch duration: this run"}
     achieved = alg_8d / t_dom / 1e9
     step_bytes = 0.75 * b * M + 36.0 * (8 + S) * M                        # SURVEY.md 8d whole-step figure: 0.75 + 36 (C+S)/b per genotype
-    per_step_units = (gb if snp else b * world) * M
-    cfg_name = {(100_000, 500_000, (8,)): "configs[3]", (500_000, 1_000_000, (16,)): "configs[4]", (2504, 600_000, (7,)): "configs[1]",
-                (2504, 600_000, tuple(range(2, 11))): "configs[2]"}.get((args.rows, M, tuple(ks)), "configs[3] shape, resized")
-    mode = "snp" if snp else ("dp-global-batch" if args.global_batch is not None else "dp")
-    out = {
-        "metric": "genotypes/sec (samples x SNPs / epoch-sec) at K=%s" % (K if len(ks) == 1 else f"{ks[0]}..{ks[-1]}"),
-        "value": per_step_units * args.steps / dt, "unit": "genotypes/s",
-        "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong" if args.global_batch is not None else "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{cfg_name}: synthetic {args.rows} samples x {M} SNPs, K={'/'.join(map(str, ks))}, 2-bit packed resident in HBM, "
-                               f"{'SNP' if snp else 'sample'}-sharded over {world} GPU(s), batch {b}/GPU, hidden {args.hidden}, n_components 8, "
-                               f"loss value {'every step' if with_loss else 'skipped'}",
-                   "global_batch": gb if snp else b * world, "parallelism": f"{args.parallelism}{world}", "mode": mode,
-                   "clock_ramp_steps_untimed": n_ramp, "transport": comm.kind if comm is not None else None,
-                   "emulated_world": args.emulate_world,
-                   "message_b_buckets": eng.lay.n_buckets if ddp else None, "pass3_in_ranges": (not args.p3_whole) if ddp else None,
-                   "second_communicator": (eng.comm_a is not None) if ddp else None},
-        # one C call per step (nadm_step): host time to queue a step onto an idle device; the timed region's own loop took
-        # t_queued to queue (GPU-bound: the launch queue stays ahead)
-        "host_queue_ms_per_step": host_queue_ms, "host_loop_ms_per_step_in_timed_region": t_queued / args.steps * 1e3,
-        # bound: what binds the kernel (VALU + matrix instruction issue: issue_frac of all SIMD-cycles); roof_8d: the roof SURVEY 8d prices
-        # it against (achieved / peak / frac are in that accounting)
-        "roofline": {"bound": "valu_issue", "roof_8d": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "frac_8d": achieved / HBM_PEAK_GBS, "frac_min": alg_min / t_dom / 1e9 / HBM_PEAK_GBS,
-                     # what the counters say the launch is bound by: the fraction of all SIMD-cycles of the launch spent issuing VALU and
-                     # matrix instructions (they do not overlap on a SIMD)
-                     "issue_frac": (issue["simd_valu_busy_frac"] + issue["simd_mfma_busy_frac"]) if issue and issue["simd_valu_busy_frac"] is not None else None,
-                     "valu_busy_frac": issue["simd_valu_busy_frac"] if issue else None, "mfma_busy_frac": issue["simd_mfma_busy_frac"] if issue else None,
-                     "x_walks": x_walks, "bytes_incl_x_rewalks": alg_8d + (x_walks - 1) * rows_b * m_loc / 4,
-                     "traffic": hbm["traffic_bytes_per_launch"] if hbm else None,
-                     "traffic_source": (f"profiles/{PROFILE_ROUND}_pmc_hbm.json (replayed, not measured in this run: separate --pmc passes of FETCH_SIZE and WRITE_SIZE; {hbm['correction']}; src_hash {hbm['src_hash']})"
-                                        if hbm else None),
-                     "issue_source": (f"profiles/{PROFILE_ROUND}_pmc_sq.json (replayed, not measured in this run: separate --pmc passes of the SQ counters on "
-                                      f"the same kernel sources and workload; src_hash {sq['src_hash']})" if sq else None),
-                     "traffic_composition": composition,
-                     "kernel_ms": kms, "alg_bytes_per_launch": alg_8d, "alg_bytes_min_per_launch": alg_min,
-                     "alg_bytes_note": "frac/frac_8d: 2-bit pass over the batch + %d B per P parameter (SURVEY 8d rule; %s); frac_min: the same pass "
-                                       "+ %d B per P parameter, the bytes the launch has to move" % (
-                                           36 if fused else 8, "Adam on P fused into the launch, no dP round trip" if fused else "read P, write dP; Adam is a separate launch",
-                                           24 if fused else 8),
-                     "issue": issue, "workload_key": wk,
-                     "whole_step": {"alg_bytes": step_bytes, "achieved": step_bytes / (dt / args.steps) / 1e9,
-                                    "frac": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
-                     # algorithmic flops per genotype = 4C + 6S (X.V, Q.P^T, dP, dQ, dV)
-                     "mfma": {"alg_flops_per_genotype": 4 * 8 + 6 * S,
-                              "achieved_tflops": b * M * args.steps / dt * (4 * 8 + 6 * S) / 1e12,
-                              "peak_tflops": MFMA_BF16_PEAK_TFLOPS,
-                              "frac": b * M * args.steps / dt * (4 * 8 + 6 * S) / 1e12 / MFMA_BF16_PEAK_TFLOPS}},
-        "loss_last_step": loss_last,
-        "epoch_loop": full_run,
-        "box": box,
-    }
-    if world > 1:
-        out["ms_per_step_this_rank"] = dt_rank / args.steps * 1e3          # rank 0's own clock; ms_per_step is the max over ranks
-    if args.share_gpu:
-        out["config"]["share_gpu"] = "all ranks on cuda:0 over gloo: functional check, not a measurement"
+    # one C call per step (nadm_step): host time to queue a step onto an idle device
+    out["host_queue_ms_per_step"] = host_queue_ms
+    # bound: what binds the kernel (VALU + matrix instruction issue: issue_frac of all SIMD-cycles); roof_8d: the roof SURVEY 8d prices
+    # it against (achieved / peak / frac are in that accounting)
+    out["roofline"] = {"bound": "valu_issue", "roof_8d": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "frac_8d": achieved / HBM_PEAK_GBS, "frac_min": alg_min / t_dom / 1e9 / HBM_PEAK_GBS,
+                       # what the counters say the launch is bound by: the fraction of all SIMD-cycles of the launch spent issuing VALU and
+                       # matrix instructions (they do not overlap on a SIMD)
+                       "issue_frac": (issue["simd_valu_busy_frac"] + issue["simd_mfma_busy_frac"]) if issue and issue["simd_valu_busy_frac"] is not None else None,
+                       "valu_busy_frac": issue["simd_valu_busy_frac"] if issue else None, "mfma_busy_frac": issue["simd_mfma_busy_frac"] if issue else None,
+                       "x_walks": x_walks, "bytes_incl_x_rewalks": alg_8d + (x_walks - 1) * rows_b * m_loc / 4,
+                       "traffic": hbm["traffic_bytes_per_launch"] if hbm else None,
+                       "traffic_source": (f"profiles/{PROFILE_ROUND}_pmc_hbm.json (replayed, not measured in this run: separate --pmc passes of FETCH_SIZE and WRITE_SIZE; {hbm['correction']}; src_hash {hbm['src_hash']})"
+                                          if hbm else None),
+                       "issue_source": (f"profiles/{PROFILE_ROUND}_pmc_sq.json (replayed, not measured in this run: separate --pmc passes of the SQ counters on "
+                                        f"the same kernel sources and workload; src_hash {sq['src_hash']})" if sq else None),
+                       "traffic_composition": composition,
+                       "kernel_ms": kms, "alg_bytes_per_launch": alg_8d, "alg_bytes_min_per_launch": alg_min,
+                       "alg_bytes_note": "frac/frac_8d: 2-bit pass over the batch + %d B per P parameter (SURVEY 8d rule; %s); frac_min: the same pass "
+                                         "+ %d B per P parameter, the bytes the launch has to move" % (
+                                             36 if fused else 8, "Adam on P fused into the launch, no dP round trip" if fused else "read P, write dP; Adam is a separate launch",
+                                             24 if fused else 8),
+                       "issue": issue, "workload_key": wk,
+                       "whole_step": {"alg_bytes": step_bytes, "achieved": step_bytes / (dt / args.steps) / 1e9,
+                                      "frac": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
+                       # algorithmic flops per genotype = 4C + 6S (X.V, Q.P^T, dP, dQ, dV)
+                       "mfma": {"alg_flops_per_genotype": 4 * 8 + 6 * S,
+                                "achieved_tflops": b * M * args.steps / dt * (4 * 8 + 6 * S) / 1e12,
+                                "peak_tflops": MFMA_BF16_PEAK_TFLOPS,
+                                "frac": b * M * args.steps / dt * (4 * 8 + 6 * S) / 1e12 / MFMA_BF16_PEAK_TFLOPS}}
+    out["epoch_loop"] = full_run
+    out["box"] = box
     if ((world > 1 and not args.no_alt) or args.alt) and not snp and args.emulate_world is None:
         headline = {"ms_per_step": out["ms_per_step"], "value": out["value"], "unit": "genotypes/s", "steps": args.steps,
                     "rows_per_rank_per_step": b, "global_batch": b * world}
@@ -828,25 +909,9 @@ def main():
             os._exit(0)
         alt_guard.cancel()
         os.close(saved_stdout_fd)
-    if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and len(ks) == 1 and args.emulate_world is None:
-            out["cpu_baseline"] = cpu_baseline(eng, args, dev)
-            out["cpu_baseline_reference_shaped"] = cpu_baseline_reference_shaped(eng, args, dev)
-        problems = validate_line(out, world)
-        if problems:
-            print(f"[bench] incomplete line: {problems}", file=sys.stderr)
-        print(json.dumps(out))
-        sys.stdout.flush()
-    if hang_guard is not None:
-        hang_guard.cancel()
-    comm_a2 = eng.comm_a
-    if comm is not None:                                                # every rank gets here: the communicator goes down together
-        del eng
-        comm.close()
-        if comm_a2 is not None:
-            comm_a2.close()
-    if use_dist:
-        dist.destroy_process_group()
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and len(ks) == 1 and args.emulate_world is None:
+        out["cpu_baseline"] = cpu_baseline(eng, args, dev)
+        out["cpu_baseline_reference_shaped"] = cpu_baseline_reference_shaped(eng, args, dev)
 
 
 if __name__ == "__main__":

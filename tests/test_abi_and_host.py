@@ -434,12 +434,13 @@ def test_rsvd_matches_reference_on_demo():
     from neural_admixture_amd.io import PackedGenotypes
     d = np.load(f"{G}/demo_k3.npz")
     Gm = O.unpack2bit(d["G_packed"], int(d["M"]))
-    V = RSVD(Gm, Gm.shape[0], Gm.shape[1], 8, int(d["seed"]), device=None)
+    host = torch.device("cpu")                          # device=None would pick the GPU wherever there is one
+    V = RSVD(Gm, Gm.shape[0], Gm.shape[1], 8, int(d["seed"]), device=host)
     assert V.shape == d["Vt"].shape and np.abs(V - d["Vt"]).max() < 1e-5
     ld = d["G_packed"].shape[1] + (-d["G_packed"].shape[1]) % 16
     pk = np.zeros((Gm.shape[0], ld), dtype=np.uint8)
     pk[:, :d["G_packed"].shape[1]] = d["G_packed"]
-    V2 = RSVD(PackedGenotypes(torch.from_numpy(pk), Gm.shape[0], Gm.shape[1]), Gm.shape[0], Gm.shape[1], 8, int(d["seed"]), device=None)
+    V2 = RSVD(PackedGenotypes(torch.from_numpy(pk), Gm.shape[0], Gm.shape[1]), Gm.shape[0], Gm.shape[1], 8, int(d["seed"]), device=host)
     assert np.abs(V2 - d["Vt"]).max() < 1e-5
 
 

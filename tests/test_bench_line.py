@@ -1,5 +1,5 @@
 """The bench line's schema (r06): what the driver reads, and -- with several ranks -- every alternative multi-GPU leg and every
-collective of the micro-benchmark, so that ONE `bench.py --gpus 8` run on a real node answers DESIGN.md section 5's open questions."""
+collective of the micro-benchmark, so that ONE `bench.py --gpus 8 --full` run on a real node answers DESIGN.md section 5's open questions."""
 import json
 import os
 import subprocess
@@ -33,7 +33,7 @@ def test_bench_share_gpu_runs_every_leg_and_prints_one_valid_line(world):
     import bench
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--share-gpu", "--rows", "8000", "--snps", "40000",
                         "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--alt-steps", "2", "--alt-warmup", "1", "--coll-reps", "2",
-                        "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                                                 # ONE JSON line on stdout, whatever the libraries print
@@ -47,7 +47,7 @@ def test_bench_share_gpu_runs_every_leg_and_prints_one_valid_line(world):
 def test_bench_one_gpu_line_carries_a_measured_clock_and_a_box_fingerprint():
     import bench
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "8000", "--snps", "200000", "--steps", "5", "--warmup", "2",
-                        "--ramp-ms", "50", "--no-cpu-baseline", "--no-epoch-loop"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--ramp-ms", "50", "--no-cpu-baseline", "--no-epoch-loop", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert bench.validate_line(d, 1) == []
@@ -64,7 +64,7 @@ def test_bench_prints_its_headline_when_the_alternative_legs_run_out_of_time():
     line -- the headline, alt = null, alt_error saying why -- and the launcher exits 0."""
     import bench
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--rows", "8000", "--snps", "40000",
-                        "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--alt-steps", "200", "--alt-deadline", "1", "--no-cpu-baseline"],
+                        "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--alt-steps", "200", "--alt-deadline", "1", "--no-cpu-baseline", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -72,3 +72,35 @@ def test_bench_prints_its_headline_when_the_alternative_legs_run_out_of_time():
     d = json.loads(lines[0])
     assert d["alt"] is None and "did not complete within" in d["alt_error"] and d["value"] > 0 and d["n_gpus"] == 2
     assert [p for p in bench.validate_line(d, 2) if not p.startswith(("alt.", "collectives."))] == []
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_times_the_steps_only_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run prints the headline without what --full adds, and --dump-outputs writes the last timed step's parameters and loss:
+    float32 / float64, within the size cap, the same in two runs whose clock ramps took different numbers of steps."""
+    import numpy as np
+    import bench
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows", "8000", "--snps", "40000", "--steps", "7",
+                            "--warmup", "2", "--ramp-ms", "100", "--dump-outputs", str(tmp_path / run)], cwd=ROOT, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, out
+        lines.append(json.loads(out[0]))
+    for d in lines:
+        assert bench.validate_line(d, 1) == [] and d["full"] is False and d["steps"] == 7 and d["ms_per_step"] > 0
+        assert not {"roofline", "box", "epoch_loop", "cpu_baseline", "host_queue_ms_per_step", "alt"} & set(d)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"V.npy", "P_k8.npy", "g.npy", "W1.npy", "b1.npy", "Wk_k8.npy", "bk_k8.npy", "loss.npy"} == set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all()
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= bench.DUMP_BYTES
+    assert np.load(tmp_path / "a" / "P_k8.npy").shape == (40000, 8)
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == lines[0]["loss_last_step"]

@@ -7,7 +7,7 @@ if [ -n "$ABL_ONLY" ]; then for n in $ABL_ONLY; do list="$list tools/abl/$n.so";
 for so in $list; do
   for fl in "" "--no-loss"; do
     lib=""; [ "$so" != "DEFAULT" ] && lib=$PWD/$so
-    out=$(NADM_LIB=$lib python bench.py --steps 60 --warmup 10 --ramp-ms 300 --no-cpu-baseline $fl "$@" 2>/dev/null | tail -1)
+    out=$(NADM_LIB=$lib python bench.py --full --steps 60 --warmup 10 --ramp-ms 300 --no-cpu-baseline $fl "$@" 2>/dev/null | tail -1)
     echo "$(basename $so .so) ${fl:-loss} $(python3 -c "
 import json,sys
 d=json.loads(sys.argv[1]); k=d['roofline']['kernel_ms']; print('ms/step', round(d['ms_per_step'],4), ' '.join(f'{n}={v*1e3:.1f}' for n,v in k.items()), 'loss', d['loss_last_step'])" "$out")"

@@ -9,7 +9,7 @@ for rows in 20000 100000; do
   for set in "TCP_UTCL1_REQUEST_sum TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum" "TCP_UTCL1_SERIALIZATION_STALL TCP_UTCL1_STALL_INFLIGHT_MAX TCP_UTCL1_TRANSLATION_MISS_UNDER_MISS GRBM_UTCL2_BUSY GRBM_GUI_ACTIVE"; do
     i=$((i+1))
     rm -rf /tmp/pmc_t$i
-    (cd /tmp && rocprofv3 --pmc $set -d /tmp/pmc_t$i -o run -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --rows $rows > /tmp/pmc_t$i.log 2>&1)
+    (cd /tmp && rocprofv3 --pmc $set -d /tmp/pmc_t$i -o run -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --rows $rows > /tmp/pmc_t$i.log 2>&1)
     db=$(find /tmp/pmc_t$i -name "*.db" | head -1)
     echo "## rows=$rows"
     python $R/tools/pmc_summary.py $db encode_ 2>&1 || tail -5 /tmp/pmc_t$i.log

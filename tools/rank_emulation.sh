@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 {
 echo "# r06 rank emulation on one MI355X (tools/rank_emulation.sh): ms/step, host ms to queue a step, kernel_ms (us); b = rows per rank"
 echo "# weak = 800 rows per rank; strong = the reference's batch_size // num_gpus at --batch_size 800 (neural_admixture.py:287)"
-row() { python bench.py --no-cpu-baseline --steps 100 --warmup 30 "$@" 2>/dev/null | python -c "
+row() { python bench.py --full --no-cpu-baseline --steps 100 --warmup 30 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-64s' % '$*', '| ms/step', '%.4f' % d['ms_per_step'], '| host', '%.4f' % d['host_queue_ms_per_step'], '|', {k: (round(v*1e3,1) if not isinstance(v, list) else [round(x*1e3,1) for x in v]) for k,v in d['roofline']['kernel_ms'].items()})"; }
 row
