@@ -63,6 +63,7 @@ class PlanDesc(C.Structure):
 
 
 MODE_SINGLE, MODE_DP, MODE_SNP = 0, 1, 2
+PRECISION_HIGHEST, PRECISION_MEDIUM = 0, 1                 # NADM_PRECISION_* (nadm_plan_set_precision)
 T_NAMES = ("encode_fwd", "mlp_fwd", "decode_bce", "mlp_bwd", "encode_bwd", "sync_a", "sync_b")     # NADM_T_* slots
 
 
@@ -156,6 +157,8 @@ def _load():
         "nadm_plan_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(i32)]),
         "nadm_plan_bucket_ms": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(i32)]),
         "nadm_plan_poisoned": (i32, [vp]),
+        "nadm_plan_set_precision": (C.c_int, [vp, i32]),
+        "nadm_plan_precision": (i32, [vp]),
         "nadm_calib_clock": (C.c_int, [i32, vp, i32, vp, vp]),
         "nadm_wall_clock_khz": (i64, []),
         "nadm_clock_probe": (None, [vp]),

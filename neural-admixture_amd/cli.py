@@ -21,6 +21,12 @@ logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(message)s")
 log = logging.getLogger(__name__)
 
 
+def _add_precision(p):
+    p.add_argument("--precision", choices=("highest", "medium"), default="highest",
+                   help="matmul precision of the genotype passes: 'highest' (fp32-class products, default) or 'medium' (bf16-class, "
+                        "what the reference's torch.set_float32_matmul_precision('medium') gives)")
+
+
 def parse_train_args(argv):
     p = argparse.ArgumentParser(prog="neural-admixture train", description="Rapid population clustering with autoencoders - training mode")
     p.add_argument("--epochs", type=int, default=250)
@@ -50,6 +56,7 @@ def parse_train_args(argv):
     p.add_argument("--share_gpu", action="store_true",
                    help="functional check of a --num_gpus N run on a ONE-GPU box: every rank uses cuda:0 and gloo carries the "
                         "tensors (RCCL refuses two ranks per device)")
+    _add_precision(p)
     return p.parse_args(argv)
 
 
@@ -63,6 +70,7 @@ def parse_infer_args(argv):
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--num_gpus", type=int, default=1)
     p.add_argument("--threads", type=int, default=1)
+    _add_precision(p)
     return p.parse_args(argv)
 
 
@@ -99,7 +107,7 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
     K = args.k
     Ps, Qs, model = train(args.epochs, args.batch_size, args.learning_rate, K, args.seed, data, device, num_gpus, args.hidden_size,
                           master, V, pops, args.min_k, args.max_k, args.n_components, parallelism=args.parallelism,
-                          host_threads=args.threads, gmm=args.gmm)
+                          host_threads=args.threads, gmm=args.gmm, precision=args.precision)
     if master:
         save_model(model, args.name, args.save_dir)
         write_outputs(Qs, args.name, K, args.min_k, args.max_k, args.save_dir, Ps)
@@ -155,7 +163,9 @@ def main(argv=None):
         cfg = json.load(fb)
     sd = torch.load(f"{args.save_dir}/{args.name}.pt", map_location="cpu", weights_only=True)
     model = Q_P(int(cfg["hidden_size"]), int(cfg["num_features"]), ks_list=cfg["ks"], is_train=False)
-    model.load_state_dict(sd, device=torch.device("cuda:0"), max_batch=args.batch_size)
+    if args.precision != "highest":
+        log.info(f"    Matmul precision: {args.precision} (bf16-class products in the genotype passes).")
+    model.load_state_dict(sd, device=torch.device("cuda:0"), max_batch=args.batch_size, precision=args.precision)
     data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True)
     eng = model.engine
     eng.pack_from_host(data)

@@ -175,7 +175,8 @@ __device__ __forceinline__ int64_t xcd_chunk(const unsigned bid, const unsigned 
     return (int64_t)(x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / NX;
 }
 
-template <int CP>
+// MED (precision "medium", nadm_plan_set_precision): V enters as hi + mid only -- the [lo | 0] operands and their MFMA are gone
+template <int CP, bool MED = false>
 __global__ __launch_bounds__(512) void encode_fwd_mfma_kernel(const uint8_t* __restrict__ xp, int64_t ld,
                                                               const int32_t* __restrict__ idx, int b, int64_t M,
                                                               const float* V, float* __restrict__ zpart, int tiles_per_block,
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(512) void encode_fwd_mfma_kernel(const uint8_t* __r
     // 64 dword loads per thread whose lanes touch 4 different sectors each: 4.5 us of the kernel's 41, profiles/r03_ablations.txt).
     // Row m of the slice sits at float offset 8 m + 8 (m >> 6): the skew makes the column reads below (lanes = 4 row groups x 8
     // columns, rows 64 apart) hit 32 different banks.
-    bf16x8 b1[8], b2[8];
+    bf16x8 b1[8], b2[MED ? 1 : 8];
     {
         float* const sv = &s_raw[wave * SV_WAVE];
         float4 vst[CP];
@@ -272,7 +273,7 @@ __global__ __launch_bounds__(512) void encode_fwd_mfma_kernel(const uint8_t* __r
                 w2[d] = lo & ~upper;
             }
             b1[s8] = __builtin_bit_cast(bf16x8, make_uint4(w1[0], w1[1], w1[2], w1[3]));
-            b2[s8] = __builtin_bit_cast(bf16x8, make_uint4(w2[0], w2[1], w2[2], w2[3]));
+            if constexpr (!MED) b2[s8] = __builtin_bit_cast(bf16x8, make_uint4(w2[0], w2[1], w2[2], w2[3]));
         }
     }
     __syncthreads();
@@ -329,13 +330,14 @@ __global__ __launch_bounds__(512) void encode_fwd_mfma_kernel(const uint8_t* __r
                         const bf16x8 av = __builtin_bit_cast(bf16x8, make_uint4(fp4_bf16_pair(ev, 2 * hf), fp4_bf16_pair(ev, 2 * hf + 1),
                                                                                 fp4_bf16_pair(od, 2 * hf), fp4_bf16_pair(od, 2 * hf + 1)));
                         d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b1[s8], d1, 0, 0, 0);
-                        d2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b2[s8], d2, 0, 0, 0);
+                        if constexpr (!MED) d2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b2[s8], d2, 0, 0, 0);
                     }
                 }
                 // D rows = samples 4q + r, column = i: fold [hi | mid] + [lo | 0] -> columns 0..7
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float u2 = d1[r] + d2[r];
+                    float u2 = d1[r];
+                    if constexpr (!MED) u2 += d2[r];
                     u2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(u2), 0x128 /*row_ror:8*/, 0xf, 0xf, false));
                     if (i < 8) s_z[buf][wave][u][(4 * q + r) * 8 + i] = u2;
                 }
@@ -772,7 +774,10 @@ constexpr int BF_TS = NADM_BF_TS;       // samples per LDS tile
 // PROBE: the measurement build of the S = 1 form (nadm_clock_probe): launched only while a probe pointer is set, so that the kernel every
 // other launch runs is instruction for instruction the one without it (as an always-present run-time branch the probe cost 0.8 %: an extra
 // scalar load + wait in the prologue)
-template <int KP, bool LOSS, bool UNIT_P = true, bool QIMG = false, bool SLICED = false, bool PROBE = false>
+// MED: precision "medium" (nadm_plan_set_precision): P and Q enter R^T as hi + mid (the products with a lo piece are
+// dropped), dR is ONE bf16 piece (round to nearest even), no remainder, no lo half in the transposition buffer.  Q operands from the
+// tile images only (the step's form); the images are the same as for "highest" -- the lo pieces in them meet zeros or no MFMA.
+template <int KP, bool LOSS, bool UNIT_P = true, bool QIMG = false, bool SLICED = false, bool PROBE = false, bool MED = false>
 __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(bf_wpe(KP), bf_wpe(KP)))) void decode_bce_bf16_kernel(
     const uint8_t* __restrict__ xp, int64_t ld, const int32_t* __restrict__ idx, int b, int64_t M,
     float* P, const float* __restrict__ Q, int SP,
@@ -783,6 +788,7 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
     // (s_memtime) and the constant-rate one (s_memrealtime): cycles / ticks x rate = the clock THIS kernel ran at in THIS run -- a denser
     // stream than any calibration kernel, it clocks lower on the same box, and by how much is the box's business (S = 1 form only)
     static_assert(!(PROBE && SLICED), "the probe brackets the S = 1 form");
+    static_assert(!MED || (QIMG && !PROBE), "the medium form is the step's: Q images, no probe twin");
     const bool probe = PROBE && clk != nullptr && blockIdx.x == (gridDim.x >> 1);
     unsigned long long pc0 = 0, pr0 = 0;
     if (probe) { pc0 = __builtin_readcyclecounter(); pr0 = __builtin_amdgcn_s_memrealtime(); }
@@ -870,7 +876,7 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
     }
     auto p_at = [&](int64_t m, int k) -> float { return s_p[(int)(m - chunk * (MF_WAVES * 16 * NTW)) * KP + k]; };   // rows past M hold zeros
     // ---- resident A operands built from P ----
-    uint4 pa_r1[NTW], pa_r2[NTW], pa_r3[W ? NTW : 1];     // R^T: lane (row = SNP n, slot a)
+    uint4 pa_r1[NTW], pa_r2[NTW], pa_r3[W && !MED ? NTW : 1];     // R^T: lane (row = SNP n, slot a)
 #pragma unroll
     for (int t = 0; t < NTW; ++t) {
         const int64_t m = snp_of(t, n >> 2, n & 3);
@@ -891,16 +897,22 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
         if constexpr (W) {
             pa_r1[t] = H;                                                                        // slots [Ph Ph' Ph Ph']
             pa_r2[t] = Md;                                                                       // slots [Pm Pm' Pm Pm']
+            if constexpr (!MED)
             pa_r3[t] = make_uint4((H.x & m01) | (Lo.x & ~m01), (H.y & m01) | (Lo.y & ~m01), (H.z & m01) | (Lo.z & ~m01),
                                   (H.w & m01) | (Lo.w & ~m01));                              // slots [Ph Ph' Pl Pl']
         } else if constexpr (ONE) {
             const uint32_t m2 = lt_mask(a, 3) & ~m01;                                            // a == 2
+            if constexpr (MED)                                                                   // slots [Ph|Ph Pm|Pm 0 0]
+                pa_r1[t] = make_uint4((H.x & m0) | (Md.x & m1), (H.y & m0) | (Md.y & m1), (H.x & m0) | (Md.x & m1), (H.y & m0) | (Md.y & m1));
+            else
             pa_r1[t] = make_uint4((H.x & (m0 | m2)) | (Md.x & m1), (H.y & (m0 | m2)) | (Md.y & m1),
                                   (H.x & m0) | (Md.x & m1) | (Lo.x & m2), (H.y & m0) | (Md.y & m1) | (Lo.y & m2));   // slots [Ph|Ph Pm|Pm Ph|Pl 0]
             pa_r2[t] = make_uint4(0, 0, 0, 0);
         } else {
             pa_r1[t] = make_uint4((H.x & m01) | (Md.x & ~m01), (H.y & m01) | (Md.y & ~m01), (H.z & m01) | (Md.z & ~m01),
                                   (H.w & m01) | (Md.w & ~m01));                              // slots [Ph Ph Pm Pm]
+            if constexpr (MED) pa_r2[t] = make_uint4(0, 0, 0, 0);                              // (no second MFMA)
+            else
             pa_r2[t] = make_uint4((H.x & m0) | (Lo.x & m1), (H.y & m0) | (Lo.y & m1), (H.z & m0) | (Lo.z & m1),
                                   (H.w & m0) | (Lo.w & m1));                                 // slots [Ph Pl 0 0]
         }
@@ -1061,8 +1073,8 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
         D = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_r1[t]), as_bf16x8(q1), D, 0, 0, 0);
         if constexpr (W) {
             D = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_r2[t]), as_bf16x8(q1), D, 0, 0, 0);
-            D = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_r3[t]), as_bf16x8(q2), D, 0, 0, 0);
-        } else if constexpr (!ONE) {
+            if constexpr (!MED) D = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_r3[t]), as_bf16x8(q2), D, 0, 0, 0);
+        } else if constexpr (!ONE && !MED) {
             D = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_r2[t]), as_bf16x8(q2), D, 0, 0, 0);
         }
         return D;
@@ -1113,18 +1125,20 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
                                     bce_loss_exact2<UNIT_P>(d, (f32x2_t){1.f, 1.f} - d, x, lossacc);
                                 const uint32_t hp = __builtin_bit_cast(uint32_t, __builtin_convertvector(dR, bf16x2_t));
                                 hi[t2][h2] = hp;
+                                if constexpr (MED) continue;                   // dR as one piece (RNE)
                                 const f32x2_t rem = dR - (f32x2_t){__uint_as_float(hp << 16), __uint_as_float(hp & 0xFFFF0000u)};
                                 lo[t2][h2] = __builtin_bit_cast(uint32_t, __builtin_convertvector(rem, bf16x2_t));
                             }
                             // transposition buffer of this SNP tile: T[t2][hl][sample 16*s2 + n][SNP 4a .. 4a+3]  (row = 16 bf16 = 32 B)
                             *reinterpret_cast<uint2*>(tw + (2 * t2 + 0) * TWP + (16 * s2 + n) * TWS + 4 * wchunk) = make_uint2(hi[t2][0], hi[t2][1]);
-                            *reinterpret_cast<uint2*>(tw + (2 * t2 + 1) * TWP + (16 * s2 + n) * TWS + 4 * wchunk) = make_uint2(lo[t2][0], lo[t2][1]);
+                            if constexpr (!MED)
+                                *reinterpret_cast<uint2*>(tw + (2 * t2 + 1) * TWP + (16 * s2 + n) * TWS + 4 * wchunk) = make_uint2(lo[t2][0], lo[t2][1]);
                         }
                         // dQ^T of this sample tile: the lane's 8 dR values (2 tiles x 4 SNPs) are the B operand
                         const bf16x8 bh = as_bf16x8(make_uint4(hi[0][0], hi[0][1], hi[1][0], hi[1][1]));
-                        const bf16x8 bl = as_bf16x8(make_uint4(lo[0][0], lo[0][1], lo[1][0], lo[1][1]));
+                        const bf16x8 bl = as_bf16x8(make_uint4(lo[0][0], lo[0][1], lo[1][0], lo[1][1]));     // (MED: unused)
                         dq[s2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_q1[tp]), bh, dq[s2], 0, 0, 0);
-                        dq[s2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_q1[tp]), bl, dq[s2], 0, 0, 0);
+                        if constexpr (!MED) dq[s2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_q1[tp]), bl, dq[s2], 0, 0, 0);
                         if constexpr (W) {
                             dq[s2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(pa_q2[tp]), bh, dq[s2], 0, 0, 0);
                         }
@@ -1140,13 +1154,16 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
                         const uint16_t* th = tw + (2 * t2 + 0) * TWP, *tlw = tw + (2 * t2 + 1) * TWP;
                         const s16x4_t h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(th + trow * TWS + tcol));
                         const s16x4_t h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(th + (trow + 4) * TWS + tcol4));
-                        const s16x4_t l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(tlw + trow * TWS + tcol));
-                        const s16x4_t l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(tlw + (trow + 4) * TWS + tcol4));
+                        s16x4_t l0 = {0, 0, 0, 0}, l1 = {0, 0, 0, 0};                             // (MED: no lo half)
+                        if constexpr (!MED) {
+                            l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(tlw + trow * TWS + tcol));
+                            l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(tlw + (trow + 4) * TWS + tcol4));
+                        }
                         const bf16x8 ah = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
                         const bf16x8 al = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
                         const int t = 2 * tp + t2;
                         dpacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, as_bf16x8(qd1), dpacc[t], 0, 0, 0);
-                        dpacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, as_bf16x8(qd1), dpacc[t], 0, 0, 0);
+                        if constexpr (!MED) dpacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, as_bf16x8(qd1), dpacc[t], 0, 0, 0);
                         if constexpr (W) {
                             dpacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, as_bf16x8(qd2), dpacc[t], 0, 0, 0);
                         }
@@ -1652,12 +1669,31 @@ extern "C" void nadm_clock_probe(uint64_t* out2_dev) { g_clock_probe.store(reint
 template <int KP>
 static int launch_decode_mfma(const uint8_t* xp, int64_t ld, const int32_t* idx, int b, int64_t M, float* P,
                               const float* Q, int SP, float* dP, float* dqpart, float* losspart, int with_loss,
-                              hipStream_t st, uint8_t* xg, AdamFused ad, const uint4* qimg, int n_slices, float* slab, int* slice_cnt) {
+                              hipStream_t st, uint8_t* xg, AdamFused ad, const uint4* qimg, int n_slices, float* slab, int* slice_cnt,
+                              bool medium = false) {
     static_assert(KP <= 16 && mf_chunk_snps(KP) == BF_WAVES * 16 * BF_NTW, "chunking published by nadm_decode_chunk_snps");
     const int64_t chunks = (M + mf_chunk_snps(KP) - 1) / mf_chunk_snps(KP);
     dim3 grid((unsigned)chunks, (unsigned)n_slices), block(64 * BF_WAVES);
     constexpr bool CAN_IMG = BF_TS == QI_TS;                 // (variant builds with another tile depth: decode_bce_impl refuses qimg)
     unsigned long long* const clk_probe = g_clock_probe.load();
+    if (medium) {               // precision "medium": the Q-image forms only (decode_bce_impl refuses the rest), no probe twin
+#define NADM_P2_LAUNCH_MED(...)                                                                                                                 \
+    do {                                                                                                                                       \
+        if (n_slices > 1)                                                                                                                      \
+            hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, __VA_ARGS__, CAN_IMG, true, false, true>), grid, block, 0, st, xp, ld, idx, b, M, P, \
+                               Q, SP, dP, dqpart, losspart, xg, ad, qimg, slab, slice_cnt, (unsigned long long*)nullptr);                     \
+        else                                                                                                                                   \
+            hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, __VA_ARGS__, CAN_IMG, false, false, true>), grid, block, 0, st, xp, ld, idx, b, M, \
+                               P, Q, SP, dP, dqpart, losspart, xg, ad, qimg, slab, slice_cnt, (unsigned long long*)nullptr);                  \
+    } while (0)
+        if constexpr (CAN_IMG) {
+            if (with_loss & 2) NADM_P2_LAUNCH_MED(true, false);
+            else if (with_loss) NADM_P2_LAUNCH_MED(true, true);
+            else NADM_P2_LAUNCH_MED(false, true);
+        }
+#undef NADM_P2_LAUNCH_MED
+        return check_launch("decode_bce_bf16 (medium)");
+    }
 #define NADM_P2_LAUNCH(...)                                                                                                                     \
     do {                                                                                                                                       \
         if (n_slices > 1)                                                                                                                      \
@@ -1737,7 +1773,8 @@ static int enc_rows_per_block(int b) {
 
 static int encode_fwd_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                            const float* V, int32_t CP, float* zpart, void* stream, uint32_t missing_bf16,
-                           SmallSide ss = SmallSide{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0.f}, int64_t total_chunks = 0) {
+                           SmallSide ss = SmallSide{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0.f}, int64_t total_chunks = 0,
+                           bool medium = false) {
     if (!xp || !idx || !V || !zpart) return fail("nadm_encode_fwd: null pointer");
     if (b <= 0 || M <= 0) return fail("nadm_encode_fwd: empty batch or M");
     if (ld % 16 != 0 || ld * 4 < M) return fail("nadm_encode_fwd: ld must be a multiple of 16 and >= ceil(M/4)");
@@ -1780,7 +1817,10 @@ static int encode_fwd_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, in
         gy = (ntiles + tpb - 1) / tpb;
         const int side_blocks = ss.part ? (ss.n + 511) / 512 : 0;
         dim3 g2((unsigned)(chunks * gy + side_blocks)), b2(512);
-        if (CP == 4) hipLaunchKernelGGL((encode_fwd_mfma_kernel<4>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
+        if (medium) {          // precision "medium": V as hi + mid (the plan's step only)
+            if (CP == 4) hipLaunchKernelGGL((encode_fwd_mfma_kernel<4, true>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
+            else hipLaunchKernelGGL((encode_fwd_mfma_kernel<8, true>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
+        } else if (CP == 4) hipLaunchKernelGGL((encode_fwd_mfma_kernel<4>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
         else hipLaunchKernelGGL((encode_fwd_mfma_kernel<8>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
         return check_launch("encode_fwd_mfma");
     }
@@ -1833,9 +1873,8 @@ extern "C" int nadm_encode_fwd_part(const uint8_t* xp, int64_t ld, const int32_t
     return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0u, SmallSide{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0.f}, total_chunks);
 }
 
-extern "C" int nadm_encode_fwd_small(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                     const float* V, int32_t CP, float* zpart, const float* small_part, int32_t splits, int32_t n_small,
-                                     float* grad_small, float* small, const nadm_adam_t* adam, void* stream) {
+static int small_side_args(const float* small_part, int32_t splits, int32_t n_small, float* grad_small, float* small, const nadm_adam_t* adam,
+                           SmallSide* out) {
     if (!small_part || !grad_small) return fail("nadm_encode_fwd_small: null pointer");
     if (splits <= 0 || n_small <= 0) return fail("nadm_encode_fwd_small: empty");
     SmallSide ss{small_part, grad_small, small, nullptr, nullptr, splits, n_small, 0.f, 0.f, 0.f};
@@ -1845,6 +1884,15 @@ extern "C" int nadm_encode_fwd_small(const uint8_t* xp, int64_t ld, const int32_
         ss.m = adam->m; ss.v = adam->v; ss.grad_scale = adam->grad_scale;
         adam_scalars(adam->lr, adam->step, &ss.step_size, &ss.inv_bc2);
     }
+    *out = ss;
+    return 0;
+}
+
+extern "C" int nadm_encode_fwd_small(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                                     const float* V, int32_t CP, float* zpart, const float* small_part, int32_t splits, int32_t n_small,
+                                     float* grad_small, float* small, const nadm_adam_t* adam, void* stream) {
+    SmallSide ss;
+    if (small_side_args(small_part, splits, n_small, grad_small, small, adam, &ss)) return 1;
     return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0u, ss);
 }
 
@@ -1857,8 +1905,10 @@ extern "C" int nadm_pca_project(const uint8_t* xp, int64_t ld, const int32_t* id
 static int decode_bce_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                            float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
                            float* losspart, int32_t with_loss, void* stream, uint8_t* xg, AdamFused ad, const uint4* qimg = nullptr,
-                           int32_t n_slices = 1, float* slab = nullptr, int32_t* slice_cnt = nullptr) {
+                           int32_t n_slices = 1, float* slab = nullptr, int32_t* slice_cnt = nullptr, bool medium = false) {
     if (!xp || !idx || !P || !Q || !dP || !dqpart) return fail("nadm_decode_bce: null pointer");
+    if (medium && kp <= 16 && (!qimg || NADM_BF_TS != nadm::QI_TS))        // (kp > 16: the VALU kernel, the same under either precision)
+        return fail("nadm_step: precision \"medium\" runs pass 2 from the Q images (nadm_plan_desc_t.qimg) at padded K <= 16");
     if (ld >> 32) return fail("nadm_decode_bce: rows of 4 GiB and more (ld >= 2^32) are not supported");      // the matrix pass forms row addresses from 32-bit factors
     if (n_slices < 1 || n_slices > NADM_MAX_P2_SLICES) return fail("nadm_decode_bce_sliced: n_slices must be in 1..8");
     if (n_slices > 1) {
@@ -1877,10 +1927,10 @@ static int decode_bce_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, in
     hipStream_t st = (hipStream_t)stream;
     if (kp <= 16) {
         switch (kp) {
-            case 4: return launch_decode_mfma<4>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt);
-            case 8: return launch_decode_mfma<8>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt);
-            case 12: return launch_decode_mfma<12>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt);
-            case 16: return launch_decode_mfma<16>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt);
+            case 4: return launch_decode_mfma<4>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt, medium);
+            case 8: return launch_decode_mfma<8>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt, medium);
+            case 12: return launch_decode_mfma<12>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt, medium);
+            case 16: return launch_decode_mfma<16>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt, medium);
             default: return fail("nadm_decode_bce: unsupported padded K (use nadm_pad_k)");
         }
     }
@@ -1981,6 +2031,36 @@ extern "C" int nadm_decode_bce_sliced(const uint8_t* xp, int64_t ld, const int32
     if (ad.m && ((uintptr_t)P & 15)) return fail("nadm_decode_bce_sliced: P must be 16-byte aligned");
     return decode_bce_impl(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, stream, xg, ad, static_cast<const uint4*>(qimg),
                            n_slices, slab, counters);
+}
+
+// ---- the plan's step with its matmul precision (nadm_host.h)
+int nadm::decode_bce_prec(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, float* P, int32_t kp, const float* Q, int32_t SP,
+                          float* dP, float* dqpart, float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, const void* qimg,
+                          int32_t n_slices, float* slab, int32_t* counters, int32_t precision, void* stream) {
+    if (precision != NADM_PRECISION_MEDIUM) {                       // exactly the public forms
+        if (n_slices > 1)
+            return nadm_decode_bce_sliced(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, adam, qimg, n_slices, slab, counters, stream);
+        if (qimg) return nadm_decode_bce_images(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, adam, qimg, stream);
+        return nadm_decode_bce_step(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, adam, stream);
+    }
+    AdamFused ad;
+    if (adam_fused_args(adam, "nadm_step: Adam state is NULL", &ad)) return 1;
+    if (ad.m && ((uintptr_t)P & 15)) return fail("nadm_step: P must be 16-byte aligned");
+    return decode_bce_impl(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, stream, xg, ad, static_cast<const uint4*>(qimg),
+                           n_slices, slab, counters, true);
+}
+
+int nadm::encode_fwd_prec(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* V, int32_t CP, float* zpart,
+                          int64_t total_chunks, const float* small_part, int32_t splits, int32_t n_small, float* grad_small, float* small,
+                          const nadm_adam_t* adam, int32_t precision, void* stream) {
+    if (precision != NADM_PRECISION_MEDIUM) {                       // exactly the public forms
+        if (small_part) return nadm_encode_fwd_small(xp, ld, idx, b, M, V, CP, zpart, small_part, splits, n_small, grad_small, small, adam, stream);
+        if (total_chunks > 0) return nadm_encode_fwd_part(xp, ld, idx, b, M, V, CP, zpart, total_chunks, stream);
+        return nadm_encode_fwd(xp, ld, idx, b, M, V, CP, zpart, stream);
+    }
+    SmallSide ss{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0.f};
+    if (small_part && small_side_args(small_part, splits, n_small, grad_small, small, adam, &ss)) return 1;
+    return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0u, ss, total_chunks, CP <= 8);
 }
 
 extern "C" int64_t nadm_batch_copy_bytes(int32_t b, int64_t M) { return ((M + 4 * nadm::XG_TILE_COLS - 1) / (4 * nadm::XG_TILE_COLS)) * (int64_t)b * nadm::XG_TILE_COLS; }

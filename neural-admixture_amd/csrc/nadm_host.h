@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
+#include "../../include/nadm.h"
 
 namespace nadm {
 
@@ -31,5 +32,16 @@ inline void adam_scalars(float lr, int step, float* step_size, float* inv_bc2) {
     *step_size = (float)((double)lr / bc1);
     *inv_bc2 = (float)(1.0 / sqrt(bc2));
 }
+
+// The genotype passes as the plan's step runs them, with its matmul precision (NADM_PRECISION_*, nadm_plan_set_precision):
+// "highest" calls exactly the public entry point of that form (nadm_decode_bce_sliced / _images / _step, nadm_encode_fwd / _part /
+// _small); "medium" runs the same checks and launches the kernels' medium instantiations (nadm_genotype_passes.hip).
+int decode_bce_prec(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, float* P, int32_t kp, const float* Q, int32_t SP,
+                    float* dP, float* dqpart, float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, const void* qimg,
+                    int32_t n_slices, float* slab, int32_t* counters, int32_t precision, void* stream);
+// small_part == NULL: no side work (then total_chunks > 0 is the launch of one part of a pass, nadm_encode_fwd_part)
+int encode_fwd_prec(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* V, int32_t CP, float* zpart,
+                    int64_t total_chunks, const float* small_part, int32_t splits, int32_t n_small, float* grad_small, float* small,
+                    const nadm_adam_t* adam, int32_t precision, void* stream);
 
 }  // namespace nadm

@@ -281,6 +281,7 @@ struct nadm_plan {
     int step_count = 0;
     bool p_unit = true;
     bool poisoned = false;                                       // a step failed part-way: see include/nadm.h
+    int32_t precision = NADM_PRECISION_HIGHEST;                  // matmul precision of passes 1 and 2 (nadm_plan_set_precision)
     // what the last step left to the next one (see the head of this file)
     bool small_pending = false;
     int pend_splits = 0, pend_step = 0;
@@ -364,9 +365,9 @@ int encode_fwd_parts(nadm_plan* p, const int32_t* idx, int b, hipStream_t st) {
         if (p->b_pending) HIP_OK(hipStreamWaitEvent(fs, p->ev_g[j], 0), "hipStreamWaitEvent");
         const int64_t m0 = p->lay.bkt_m0[j], m1 = p->lay.bkt_m0[j + 1];
         if (p->nb == 1) {
-            if (nadm_encode_fwd(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, fs)) return 1;
-        } else if (nadm_encode_fwd_part(d.xp + m0 / 4, d.ld, idx, b, m1 - m0, V + m0 * hd.CP, hd.CP, d.zpart + nadm_encode_chunks(m0) * (int64_t)b * hd.CP,
-                                        p->enc_chunks, fs)) {
+            if (encode_fwd_prec(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, p->precision, fs)) return 1;
+        } else if (encode_fwd_prec(d.xp + m0 / 4, d.ld, idx, b, m1 - m0, V + m0 * hd.CP, hd.CP, d.zpart + nadm_encode_chunks(m0) * (int64_t)b * hd.CP,
+                                   p->enc_chunks, nullptr, 0, 0, nullptr, nullptr, nullptr, p->precision, fs)) {
             return 1;
         }
         if (j > 0) HIP_OK(hipEventRecord(p->ev_p1[j], fs), "hipEventRecord");
@@ -387,12 +388,13 @@ int forward(nadm_plan* p, const int32_t* idx, int b, void* stream) {
         if (encode_fwd_parts(p, idx, b, (hipStream_t)stream)) return 1;
     } else if (p->small_pending && hd.CP <= 8) {
         const nadm_adam_t sa = adam_at(p, 0, p->pend_lr, p->pend_step, p->pend_scale);
-        if (nadm_encode_fwd_small(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, d.small_part, p->pend_splits, hd.n_small, d.grads, d.params, &sa, stream))
+        if (encode_fwd_prec(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, 0, d.small_part, p->pend_splits, hd.n_small, d.grads, d.params, &sa,
+                            p->precision, stream))
             return 1;
         p->small_pending = false;
     } else {
         if (flush_small(p, stream)) return 1;
-        if (nadm_encode_fwd(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, stream)) return 1;
+        if (encode_fwd_prec(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, p->precision, stream)) return 1;
     }
     if (t1.end()) return 1;
     const float* zsrc = d.zpart;
@@ -434,19 +436,14 @@ int decode_heads(nadm_plan* p, const int32_t* idx, int b, int with_loss, const f
         nadm_adam_t ad;
         const nadm_adam_t* adp = nullptr;
         if (lr_scale) { ad = adam_at(p, p->lay.off_p[h], lr_scale[0], p->step_count, lr_scale[1]); adp = &ad; }
-        int rc;
         const void* qi = (d.qimg && kp <= 16) ? (const char*)d.qimg + (int64_t)h * d.qimg_head_bytes : nullptr;
         const int slices = d.p2_slab ? nadm_decode_slices(b, d.M, kp) : 1;     // sample slices where the SNP chunks alone leave CUs idle
         if (slices > 1 && slices > p->slices_cap[h])                           // (the rule is a function of (b, M, kp); only the test build can move it)
             return fail("nadm_step: pass 2 would be cut into more sample slices than the plan's slab was sized for at creation");
-        if (slices > 1)
-            rc = nadm_decode_bce_sliced(d.xp, d.ld, idx, b, d.M, Ph, kp, Qh, hd.SP, dPh, slab, lossp, flags, xg, adp, qi, slices,
-                                        d.p2_slab + p->slab_off[h], d.p2_cnt + p->loss_off[h], st);
-        else if (qi)
-            rc = nadm_decode_bce_images(d.xp, d.ld, idx, b, d.M, Ph, kp, Qh, hd.SP, dPh, slab, lossp, flags, xg, adp, qi, st);
-        else
-            rc = nadm_decode_bce_step(d.xp, d.ld, idx, b, d.M, Ph, kp, Qh, hd.SP, dPh, slab, lossp, flags, xg, adp, st);
-        if (rc) return 1;
+        // (sliced / from the Q images / splitting Q itself: nadm_decode_bce_sliced / _images / _step, in the plan's precision)
+        if (decode_bce_prec(d.xp, d.ld, idx, b, d.M, Ph, kp, Qh, hd.SP, dPh, slab, lossp, flags, xg, adp, qi, slices,
+                            slices > 1 ? d.p2_slab + p->slab_off[h] : nullptr, slices > 1 ? d.p2_cnt + p->loss_off[h] : nullptr, p->precision, st))
+            return 1;
         dq_off += p->dec_chunks[h] * (int64_t)b * kp;
     }
     if (fan > 1) {
@@ -596,6 +593,20 @@ extern "C" int32_t nadm_plan_p_in_unit_range(const nadm_plan_t* p) { return p &&
 extern "C" int32_t nadm_plan_step_count(const nadm_plan_t* p) { return p ? p->step_count : -1; }
 
 extern "C" int32_t nadm_plan_poisoned(const nadm_plan_t* p) { return p && p->poisoned ? 1 : 0; }
+
+extern "C" int nadm_plan_set_precision(nadm_plan_t* p, int32_t precision) {
+    if (!p) return fail("nadm_plan_set_precision: null pointer");
+    if (p->poisoned) return poisoned(p, "nadm_plan_set_precision");
+    if (precision != NADM_PRECISION_HIGHEST && precision != NADM_PRECISION_MEDIUM)
+        return fail("nadm_plan_set_precision: precision must be NADM_PRECISION_HIGHEST (0) or NADM_PRECISION_MEDIUM (1)");
+    if (precision == NADM_PRECISION_MEDIUM && !p->d.qimg)
+        for (int h = 0; h < p->d.heads.n_heads; ++h)
+            if (p->d.heads.kp[h] <= 16) return fail("nadm_plan_set_precision: \"medium\" runs pass 2 from the Q images: the plan has no qimg");
+    p->precision = precision;
+    return 0;
+}
+
+extern "C" int32_t nadm_plan_precision(const nadm_plan_t* p) { return p ? p->precision : -1; }
 
 extern "C" int nadm_plan_flush(nadm_plan_t* p, void* stream) {
     if (!p) return fail("nadm_plan_flush: null pointer");

@@ -15,6 +15,10 @@ epilogues and the hand-offs between launches live in csrc/nadm_step.hip; nothing
 ``forward`` / ``backward`` / ``adam`` below are the same step as three plain phases with the gradients left in ``gflat`` -- what
 autograd's ``loss.backward()`` + ``optimizer.step()`` expose in the reference.  The parity tests inspect gradients through them;
 the trainer does not use them.
+
+``precision`` is the matmul precision of the step and of ``infer_q`` (include/nadm.h, nadm_plan_set_precision):
+"highest" (the default: fp32-class products) or "medium" (bf16-class products, what the reference trains with:
+torch.set_float32_matmul_precision('medium')).  The plain phases compute "highest" only; on a "medium" engine they raise.
 """
 from __future__ import annotations
 
@@ -24,11 +28,12 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import lib, check, ptr, PlanDesc, MODE_SINGLE, MODE_DP, MODE_SNP, T_NAMES, MAX_BUCKETS
+from ._lib import lib, check, ptr, PlanDesc, MODE_SINGLE, MODE_DP, MODE_SNP, PRECISION_HIGHEST, PRECISION_MEDIUM, T_NAMES, MAX_BUCKETS
 from .layout import ModelLayout
 
 _f32 = torch.float32
 _MODES = {"single": MODE_SINGLE, "dp": MODE_DP, "snp": MODE_SNP}
+PRECISIONS = {"highest": PRECISION_HIGHEST, "medium": PRECISION_MEDIUM}
 _PIN_BYTES = 256 << 20                                   # the two pinned staging buffers of pack_from_host together (1024 rows each at M = 500k:
                                                          # 0.40 s per 100k rows; 256-row chunks 0.48, the packing alone 0.34 -- profiles/r05_io_timing.txt)
 
@@ -45,7 +50,10 @@ class Engine:
         return device.type == "cuda"
 
     def __init__(self, M: int, C_: int, Hd: int, ks: Sequence[int], device: torch.device, max_batch: int,
-                 mode: str = "single", comm=None, n_buckets: int = 1, comm_a=None, p3_whole: bool = False, debug: bool = False):
+                 mode: str = "single", comm=None, n_buckets: int = 1, comm_a=None, p3_whole: bool = False, debug: bool = False,
+                 precision: str = "highest"):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be 'highest' or 'medium'")
         if not self.supports(device):
             raise RuntimeError("neural_admixture_amd.Engine needs a ROCm GPU device (no CPU fallback)")
         if mode not in _MODES:
@@ -56,6 +64,7 @@ class Engine:
             raise ValueError("comm_a is the second communicator (message A) of mode 'dp'")
         self.device, self.mode, self.comm, self.comm_a = device, mode, comm, comm_a
         self.p3_whole, self.debug = bool(p3_whole), bool(debug)
+        self.precision = precision
         self.world, self.rank = (comm.world, comm.rank) if comm is not None else (1, 0)
         # "dp": message B = [small | V] travels as n_buckets SNP ranges (csrc/nadm_step.hip); the layout says how many M allows
         self.lay = L = ModelLayout(M, C_, Hd, ks, self.world if mode == "dp" else 1, n_buckets if mode == "dp" else 1)
@@ -115,6 +124,8 @@ class Engine:
         self._step_py, self._p_unit_py = 0, True         # the CPU double's counterparts of the plan's state
         if gpu:
             self._make_plan()
+            if precision != "highest":
+                check(lib.nadm_plan_set_precision(self._plan, PRECISIONS[precision]), "plan_set_precision")
 
     # ------------------------------------------------------------------ the plan
     def _make_plan(self) -> None:
@@ -362,6 +373,11 @@ class Engine:
         self.p_unit = False                                   # P may hold anything: the loss path clamps until the next restrict_P
 
     # ------------------------------------------------------------------ the step as three plain phases (gradients visible)
+    def _plain_phase(self, what: str) -> None:
+        if self.precision != "highest":
+            raise RuntimeError(f"Engine.{what}: the plain phases compute precision 'highest' only; this engine runs '{self.precision}' "
+                               "(train_step / infer_q honour it)")
+
     def encode_partial(self, idx: torch.Tensor, b: int) -> None:
         """Pass 1: per-chunk partial sums of Z = X.V for the batch rows idx (int32 [b], device) into zpart."""
         L = self.lay
@@ -383,12 +399,14 @@ class Engine:
 
     def forward(self, idx: torch.Tensor, b: int) -> None:
         """idx int32 [b] device row indices into xp.  Fills Z, rinv, Zn, H, Q."""
+        self._plain_phase("forward")
         self.encode_partial(idx, b)
         self.mlp_forward(b)
 
     def decode_all(self, idx: torch.Tensor, b: int, with_loss: bool = True, supervised: bool = True) -> int:
         """Pass 2 for every head (gradient dP -> gbig, dQ slabs -> dqpart) + the supervised term.  Returns the number of loss
         slots the MLP backward has to add up."""
+        self._plain_phase("decode_all")
         L, st, fsz = self.lay, _stream(), 4
         dq_offs, _ = L.dq_offsets(b)
         loss_offs = L.loss_offsets()
@@ -441,6 +459,7 @@ class Engine:
 
     def encode_backward(self, idx: torch.Tensor, b: int) -> None:
         """Pass 3: dV = X^T.dZ -> gbig, from the batch copy pass 2 of this step left (C <= 8), else from the resident matrix."""
+        self._plain_phase("encode_backward")
         L, st = self.lay, _stream()
         dzimg = None
         if self._dzimg is not None:
@@ -464,6 +483,7 @@ class Engine:
 
     def backward(self, idx: torch.Tensor, b: int, with_loss: bool = True) -> None:
         """Decoder + BCE fwd/bwd per head, MLP backward, dV.  Every gradient lands in gflat (gsmall / gbig are views)."""
+        self._plain_phase("backward")
         n_loss = self.decode_all(idx, b, with_loss)
         self.mlp_backward(b, n_loss if with_loss else 0)
         self.encode_backward(idx, b)

@@ -17,7 +17,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .engine import Engine
+from .engine import Engine, PRECISIONS
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(message)s")
 log = logging.getLogger(__name__)
@@ -67,12 +67,13 @@ class Q_P:
             sd[f"decoders.decoders.{i}.weight"] = (fp["P"][i] if fp else e.P(i)).detach().cpu().contiguous()
         return sd
 
-    def load_state_dict(self, sd, device: Optional[torch.device] = None, max_batch: int = 1024):
-        """Build an inference engine from a reference-format state dict (no decoders needed)."""
+    def load_state_dict(self, sd, device: Optional[torch.device] = None, max_batch: int = 1024, precision: str = "highest"):
+        """Build an inference engine from a reference-format state dict (no decoders needed).  ``precision``: the matmul precision
+        of its forward (Engine)."""
         V = sd["V"].float()
         M, C = V.shape
         dev = device or torch.device("cuda:0")
-        self.engine = Engine(M, C, self.hidden_size, self.ks_list, dev, max_batch)
+        self.engine = Engine(M, C, self.hidden_size, self.ks_list, dev, max_batch, precision=precision)
         parts = [sd["batch_norm.weight"], sd["common_encoder.0.weight"].reshape(-1), sd["common_encoder.0.bias"]]
         for i in range(len(self.ks_list)):
             parts += [sd[f"multihead_encoder.heads.{i}.weight"].reshape(-1), sd[f"multihead_encoder.heads.{i}.bias"]]
@@ -208,7 +209,8 @@ class NeuralAdmixture:
     dp_second_comm = False
 
     def __init__(self, k, epochs, batch_size, learning_rate, device, seed, num_gpus, master, pack2bit=None,
-                 min_k=None, max_k=None, supervised_loss_weight=100, loss_mode: str = "logged", parallelism: str = "dp"):
+                 min_k=None, max_k=None, supervised_loss_weight=100, loss_mode: str = "logged", parallelism: str = "dp",
+                 precision: str = "highest"):
         self.k, self.min_k, self.max_k = k, min_k, max_k
         self.ks_list = [int(k)] if k is not None else list(range(int(min_k), int(max_k) + 1))
         self.num_gpus, self.device, self.master, self.seed = num_gpus, device, master, int(seed)
@@ -220,6 +222,10 @@ class NeuralAdmixture:
         if parallelism not in ("dp", "snp"):
             raise ValueError("parallelism must be 'dp' (samples sharded, gradients summed over ranks) or 'snp' (SNPs sharded)")
         self.parallelism = parallelism
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be 'highest' (fp32-class products, the default) or 'medium' (bf16-class, the reference's "
+                             "torch.set_float32_matmul_precision('medium'))")
+        self.precision = precision       # matmul precision of the engine's step and inference (engine.py)
         self.loss_mode = loss_mode       # "logged": loss only on epochs that print it (:416); "always": every step; "steps": every step
         self.epoch_losses: dict = {}     # AND read back after each one like the reference's loss.item() (:414) -> step_losses (parity tests)
         self.step_losses: list = []
@@ -247,9 +253,9 @@ class NeuralAdmixture:
             from .comm import make_comm
             eng = self.engine_cls(M, C, hidden_size, self.ks_list, dev, max(self.batch_size, infer_b), mode="dp",
                                   comm=make_comm(dev, rank, world), n_buckets=self.dp_buckets,
-                                  comm_a=make_comm(dev, rank, world) if self.dp_second_comm else None)
+                                  comm_a=make_comm(dev, rank, world) if self.dp_second_comm else None, precision=self.precision)
         else:
-            eng = self.engine_cls(M, C, hidden_size, self.ks_list, dev, max(self.batch_size, infer_b))
+            eng = self.engine_cls(M, C, hidden_size, self.ks_list, dev, max(self.batch_size, infer_b), precision=self.precision)
         self.engine = eng
         small = init_encoder_weights(self.seed, C, hidden_size, self.ks_list)
         eng.load_params(V.detach().cpu().numpy(), P.detach().cpu().numpy(), small)
@@ -345,7 +351,8 @@ class NeuralAdmixture:
         infer_b = min(N, 1024)
         b_local = self.batch_size                                  # batch_size // num_gpus (:287)
         from .comm import make_comm
-        eng = self.engine_snp_cls(M, C, hidden_size, self.ks_list, dev, max(b_local * world, infer_b), comm=make_comm(dev, rank, world))
+        eng = self.engine_snp_cls(M, C, hidden_size, self.ks_list, dev, max(b_local * world, infer_b), comm=make_comm(dev, rank, world),
+                                  precision=self.precision)
         self.engine = eng
         small = init_encoder_weights(self.seed, C, hidden_size, self.ks_list)
         eng.load_params(V.detach().cpu().numpy(), P.detach().cpu().numpy(), small)

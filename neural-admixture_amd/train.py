@@ -13,6 +13,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .engine import PRECISIONS
 from .model import NeuralAdmixture
 from .report import loglikelihood_packed
 
@@ -183,19 +184,23 @@ def capped_host_threads(limit: int = 4):
 
 def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
           num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
-          n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto"):
+          n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto", precision: str = "highest"):
     """The reference's boundary function (see the module docstring and _train).  The host thread pools (torch intra-op, BLAS,
     OpenMP) are capped at ``host_threads`` while it runs -- the reference's CLI does that with --threads (entry.py:138-146), and
     this package's CLI passes its --threads here; the epoch loop itself always runs with torch's pool at 1 (model.py).
-    ``gmm`` (keyword, CLI --gmm): who fits the decoder-init mixture (gmm_p_init's ``fit``): "sklearn" is the reference's own call."""
+    ``gmm`` (keyword, CLI --gmm): who fits the decoder-init mixture (gmm_p_init's ``fit``): "sklearn" is the reference's own call.
+    ``precision`` (keyword, CLI --precision): the matmul precision of the training step, "highest" (fp32-class products, the default)
+    or "medium" (bf16-class: the reference's torch.set_float32_matmul_precision('medium'))."""
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be 'highest' or 'medium'")
     with capped_host_threads(max(1, int(host_threads))):
         return _train(epochs, batch_size, learning_rate, K, seed, data, device, num_gpus, hidden_size, master, V, pops, min_k, max_k,
-                      n_components, parallelism=parallelism, gmm=gmm)
+                      n_components, parallelism=parallelism, gmm=gmm, precision=precision)
 
 
 def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
            num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
-           n_components: int = None, *, parallelism: str = "dp", gmm: str = "auto"):
+           n_components: int = None, *, parallelism: str = "dp", gmm: str = "auto", precision: str = "highest"):
     """See module docstring.  ``data`` uint8 [N,M] CPU tensor (or an ``io.PackedGenotypes``, e.g. from
     ``io.read_bed_packed``); ``V`` numpy [C,M] (RSVD output,
     svd.py:83); returns Ps (list of [M,k] float32), Qs (list of [N,k] float32), model.
@@ -247,8 +252,10 @@ def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int
         if pops is not None:
             pops = torch.as_tensor(y_num, dtype=torch.int64)
 
+    if master and precision != "highest":
+        log.info(f"    Matmul precision: {precision} (bf16-class products in the genotype passes).")
     model = NeuralAdmixture(K, epochs, batch_size, learning_rate, device, seed, num_gpus, master, None, min_k, max_k,
-                            parallelism=parallelism)
+                            parallelism=parallelism, precision=precision)
     Qs, Ps, raw = model.launch_training(P_init, data, hidden_size, Vt.shape[1], Vt, M, N, pops)
 
     if master:

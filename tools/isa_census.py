@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction census of pass 2's headline instantiation (decode_bce_bf16_kernel<8, LOSS, UNIT_P, QIMG, !SLICED>) from `hipcc -S`
-(no GPU needed):  python tools/isa_census.py [-DFLAG ...] > profiles/r06_p2_isa_census.txt
+(no GPU needed):  python tools/isa_census.py [--medium] [-DFLAG ...] > profiles/r06_p2_isa_census.txt
 
 The kernel's VALU instructions are counted per REGION of the code (block prologue, per-64-sample-tile staging, the hot loop over 32-sample
 pairs, the cold exact-loss fallback, block epilogue), weighted by how often a thread runs the region at b = 800 (12.5 tiles, 25 hot-loop
@@ -8,7 +8,9 @@ rounds of 32 genotypes per lane), and the hot loop is itemised by what the instr
 (profiles/*_pmc_sq.json) is the dynamic total this static count is checked against."""
 import collections, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "decode_bce_bf16_kernelILi8ELb1ELb1ELb1ELb0E"
+# <8, LOSS, UNIT_P, QIMG, !SLICED, !PROBE, MED>: --medium selects the instantiation of precision "medium" (nadm_plan_set_precision)
+KERNEL = "decode_bce_bf16_kernelILi8ELb1ELb1ELb1ELb0ELb0ELb0EE"
+KERNEL_MEDIUM = "decode_bce_bf16_kernelILi8ELb1ELb1ELb1ELb0ELb0ELb1EE"
 B, TS = 800, 64
 
 
@@ -26,14 +28,15 @@ def valu(c):
 
 
 def main():
-    flags = sys.argv[1:]
+    flags = [f for f in sys.argv[1:] if f != "--medium"]
+    kernel = KERNEL_MEDIUM if "--medium" in sys.argv[1:] else KERNEL
     src = os.path.join(ROOT, "neural-admixture_amd", "csrc", "nadm_genotype_passes.hip")
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", out, src] + flags,
                        check=True, stderr=subprocess.DEVNULL)
         txt = open(out).read().split("\n")
-    i = next(k for k, l in enumerate(txt) if re.match(r"^_Z\w+:", l) and KERNEL in l)
+    i = next(k for k, l in enumerate(txt) if re.match(r"^_Z\w+:", l) and kernel in l)
     j = next(k for k in range(i, len(txt)) if txt[k].startswith("\t.end_amdhsa_kernel") or re.match(r"^\s*\.amdhsa_kernel", txt[k]))
     body = txt[i:j]
     meta = {}

@@ -1,10 +1,14 @@
-"""Same steps under two builds of the library (NADM_LIB): prints a checksum of every parameter after 6 steps on a few shapes."""
-import sys, hashlib, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+"""Same steps under two builds of the library (NADM_LIB): prints a checksum of every parameter after 6 steps on a few shapes.
+`headline` as the argument: the headline shape (800 rows of 500k SNPs, K = 8), a K <= 4 and a K = 16 shape instead."""
+import os, sys, hashlib, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import neural_admixture_amd as na
 from oracle import nadm_oracle as O
 dev = torch.device("cuda:0")
-for (N, M, ks, b) in ((900, 70_001, [8], 800), (300, 5003, [3], 100), (500, 20_000, [2, 5, 8], 333), (4500, 20_000, [7], 4301), (4400, 9_000, [2, 3, 9], 4099)):
+SHAPES = ((900, 70_001, [8], 800), (300, 5003, [3], 100), (500, 20_000, [2, 5, 8], 333), (4500, 20_000, [7], 4301), (4400, 9_000, [2, 3, 9], 4099))
+if sys.argv[1:] == ["headline"]:
+    SHAPES = ((900, 500_000, [8], 800), (300, 5003, [3], 100), (400, 60_000, [16], 333))
+for (N, M, ks, b) in SHAPES:
     G = O.synth_genotypes(N, M, max(ks), seed=5, missing=0.02)
     rng = np.random.default_rng(1)
     V0 = (rng.standard_normal((M, 8)) / np.sqrt(M)).astype(np.float32)
