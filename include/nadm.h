@@ -43,7 +43,7 @@ extern "C" {
 #define NADM_MAX_K 64
 #define NADM_MAX_BUCKETS 8
 #define NADM_MAX_P2_SLICES 8   /* sample slices of pass 2 (nadm_decode_bce_sliced) */
-#define NADM_ABI_VERSION 14  /* 14: nadm_clock_probe; new symbols only, same version: nadm_plan_set_precision / nadm_plan_precision (NADM_PRECISION_*); 13: pass 3 in sample slices (nadm_encode_bwd_sliced, nadm_encode_slices(_max), nadm_encode_slab_floats, nadm_encode_bwd_chunks, nadm_plan_desc_t.p3_slab / p3_cnt); 12: nadm_test_force_slices / nadm_test_force_generic_mlp exist in the test build only (-DNADM_TEST_HOOKS), nadm_calib_clock / nadm_wall_clock_khz; 11: nadm_gmm_fit_means_dev, nadm_loglik_blocks counts 8 row slices per 1024-SNP block, nadm_decode_bce_sliced / nadm_decode_slices / nadm_decode_slab_floats / nadm_test_force_slices + nadm_plan_desc_t.p2_slab / p2_cnt (pass 2 in sample slices when the SNP chunks alone do not fill the chip); 10: message B of the sample-sharded step in SNP-range buckets (nadm_flat_layout takes n_buckets, nadm_flat_layout_t.bkt_*, nadm_plan_desc_t.n_buckets / p3_whole / comm_a / debug, nadm_encode_fwd_part, nadm_plan_bucket_ms), nadm_comm_t.async_error, nadm_comm_rccl_probe, nadm_comm_rccl with a watchdog (timeout_ms), a failed step poisons its plan; 9: nadm_step / nadm_plan_* / nadm_comm_* / nadm_flat_layout (the step as one call, sharded optimizer), nadm_test_force_generic_mlp; 8: nadm_dz_image(_bytes), nadm_mlp_bwd_image; nadm_encode_bwd, nadm_encode_bwd_step, nadm_pca_project_t take the operand image of dZ / Y; 7: nadm_encode_fwd_step, nadm_sum_rows, dqpart of nadm_mlp_bwd is float* (folded in place); 6: nadm_mlp_fwd_images, nadm_decode_bce_images, nadm_q_image_bytes, nadm_encode_fwd_small; 5: nadm_adam_t.when, nadm_adam2, with_loss bit 1; 4: nadm_decode_bce_step, nadm_encode_bwd_step (nadm_adam_t, nadm_mlp_weights_t), nadm_small_grads; 3: nadm_decode_bce_gather; 2: nadm_mlp_bwd_weights, nadm_supervised_ce, nadm_pca_project(_t), nadm_loglik, nadm_savetxt_f32, nadm_decode_chunk_snps; grad_small of nadm_mlp_bwd may be NULL */
+#define NADM_ABI_VERSION 14  /* 14: nadm_clock_probe; new symbols only, same version: nadm_plan_set_precision / nadm_plan_precision (NADM_PRECISION_*), nadm_class_sums + NADM_LABEL_NONE (labels in [-1, k)); 13: pass 3 in sample slices (nadm_encode_bwd_sliced, nadm_encode_slices(_max), nadm_encode_slab_floats, nadm_encode_bwd_chunks, nadm_plan_desc_t.p3_slab / p3_cnt); 12: nadm_test_force_slices / nadm_test_force_generic_mlp exist in the test build only (-DNADM_TEST_HOOKS), nadm_calib_clock / nadm_wall_clock_khz; 11: nadm_gmm_fit_means_dev, nadm_loglik_blocks counts 8 row slices per 1024-SNP block, nadm_decode_bce_sliced / nadm_decode_slices / nadm_decode_slab_floats / nadm_test_force_slices + nadm_plan_desc_t.p2_slab / p2_cnt (pass 2 in sample slices when the SNP chunks alone do not fill the chip); 10: message B of the sample-sharded step in SNP-range buckets (nadm_flat_layout takes n_buckets, nadm_flat_layout_t.bkt_*, nadm_plan_desc_t.n_buckets / p3_whole / comm_a / debug, nadm_encode_fwd_part, nadm_plan_bucket_ms), nadm_comm_t.async_error, nadm_comm_rccl_probe, nadm_comm_rccl with a watchdog (timeout_ms), a failed step poisons its plan; 9: nadm_step / nadm_plan_* / nadm_comm_* / nadm_flat_layout (the step as one call, sharded optimizer), nadm_test_force_generic_mlp; 8: nadm_dz_image(_bytes), nadm_mlp_bwd_image; nadm_encode_bwd, nadm_encode_bwd_step, nadm_pca_project_t take the operand image of dZ / Y; 7: nadm_encode_fwd_step, nadm_sum_rows, dqpart of nadm_mlp_bwd is float* (folded in place); 6: nadm_mlp_fwd_images, nadm_decode_bce_images, nadm_q_image_bytes, nadm_encode_fwd_small; 5: nadm_adam_t.when, nadm_adam2, with_loss bit 1; 4: nadm_decode_bce_step, nadm_encode_bwd_step (nadm_adam_t, nadm_mlp_weights_t), nadm_small_grads; 3: nadm_decode_bce_gather; 2: nadm_mlp_bwd_weights, nadm_supervised_ce, nadm_pca_project(_t), nadm_loglik, nadm_savetxt_f32, nadm_decode_chunk_snps; grad_small of nadm_mlp_bwd may be NULL */
 
 /* Head table shared by the MLP entry points (mirror of NeuralEncoder/NeuralDecoder's ks list,
  * neural_admixture.py:27-29,66-76). Offsets are element offsets into the `small` flat buffer. */
@@ -276,9 +276,29 @@ int nadm_sum_rows(const float* src, int64_t rows, int64_t n, float* out, void* s
  * labels int32 [rows] = class per resident row (train.py:78-81 mapping), idx = the batch's rows (NULL: labels is
  * already per batch row); n_classes must equal k (train.py:79 asserts it).  Call after head 0's nadm_decode_bce and
  * before nadm_mlp_bwd: ADDS weight*(softmax(q_i) - onehot(y_i)) to chunk 0 of head 0's dQ slab (dqpart0 [.., b, kp])
- * and writes the weighted loss to *loss_slot (one float that nadm_mlp_bwd's n_loss range should cover). */
+ * and writes the weighted loss to *loss_slot (one float that nadm_mlp_bwd's n_loss range should cover).
+ * Labels lie in [-1, k): NADM_LABEL_NONE marks a sample without a label (semi-supervised run: a labelled panel plus query
+ * samples).  Such a row is skipped -- its dQ is not touched and it adds nothing to the loss, which is what
+ * CrossEntropyLoss(reduction='sum') does with an ignored target; the sum is NOT renormalised by the number of labelled rows.
+ * A batch with no labelled row writes 0 to *loss_slot.  A label outside [-1, k) is the caller's error (not checked on the device). */
+#define NADM_LABEL_NONE (-1)
 int nadm_supervised_ce(const float* Q, int32_t SP, int32_t k, int32_t kp, const int32_t* labels, const int32_t* idx,
                        int32_t b, int32_t n_classes, float weight, float* dqpart0, float* loss_slot, void* stream);
+
+/* Per-class genotype sums from the packed matrix: the numerator of the supervised P init (per-class mean of the RAW codes,
+ * train.py:82) in one pass over X.  sums uint32 [n_classes, M] (device, row stride M):
+ *     sums[c][m] += sum over j in [class_start[c], class_start[c+1]) of code(xp[idx[j]], m),     code = 0, 1, 2 and 3 for missing.
+ * idx int32 (device) lists the rows of xp [rows, ld] GROUPED BY CLASS (a stable argsort of the labels with the unlabelled rows
+ * dropped; entries outside [0, rows) are ignored); class_start int64 [n_classes + 1] is HOST memory, read before the call
+ * returns, non-decreasing, listing at most `rows` rows in all.  idx may be NULL when no row is listed (nothing is launched).
+ * The call ADDS: the caller zero-fills sums once, and a matrix streamed in row chunks accumulates over calls.  Integer
+ * arithmetic throughout (atomic adds where row slices share an output word), so the result is exact and independent of the order.
+ * Overflow: an entry holds at most 3 * (rows of its class, all calls together), which must fit in 32 bits -- a call refuses
+ * rows > (2^32 - 1) / 3 = 1431655765; over several calls the bound on the total is the caller's.
+ * 1 <= n_classes <= NADM_MAX_K; ld a multiple of 4 and >= ceil(M/4), xp 4-byte aligned; only SNPs < M are written and the
+ * bytes of a row past its last 32-bit word with a SNP in it are not read.  Asynchronous on `stream`. */
+int nadm_class_sums(const uint8_t* xp, int64_t ld, int64_t rows, int64_t M, const int32_t* idx, const int64_t* class_start,
+                    int32_t n_classes, uint32_t* sums, void* stream);
 
 /* The weight-gradient half of nadm_mlp_bwd on its own (dWk, dbk, dW1, db1, dg from dL, dHpre, dgp, H, Zn -> grad_small):
  * pass grad_small = NULL to nadm_mlp_bwd and call this on any stream ordered after it -- it is independent of pass 3,
@@ -436,7 +456,8 @@ typedef struct nadm_plan nadm_plan_t;
 int  nadm_plan_create(const nadm_plan_desc_t* desc, nadm_plan_t** out);
 void nadm_plan_destroy(nadm_plan_t* plan);
 int  nadm_plan_set_rows(nadm_plan_t* plan, const uint8_t* xp);
-/* supervised mode (neural_admixture.py:460-474): class per resident row, NULL switches it off */
+/* supervised mode (neural_admixture.py:460-474): class per resident row in [-1, n_classes), NADM_LABEL_NONE = no label (the row
+ * stays out of the supervised term, nadm_supervised_ce); NULL switches it off */
 int  nadm_plan_set_labels(nadm_plan_t* plan, const int32_t* labels, int32_t n_classes, float weight);
 /* Adam step count (1-based count of completed steps; 0 after loading parameters) and whether every P entry lies in [0, 1] (true
  * after any step -- restrict_P -- and for the GMM initialisation; while false the loss path clamps the reconstruction before the

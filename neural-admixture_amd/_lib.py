@@ -64,6 +64,7 @@ class PlanDesc(C.Structure):
 
 MODE_SINGLE, MODE_DP, MODE_SNP = 0, 1, 2
 PRECISION_HIGHEST, PRECISION_MEDIUM = 0, 1                 # NADM_PRECISION_* (nadm_plan_set_precision)
+LABEL_NONE = -1                                            # NADM_LABEL_NONE: a sample without a label (semi-supervised run)
 T_NAMES = ("encode_fwd", "mlp_fwd", "decode_bce", "mlp_bwd", "encode_bwd", "sync_a", "sync_b")     # NADM_T_* slots
 
 
@@ -128,6 +129,7 @@ def _load():
         "nadm_mlp_bwd_weights": (C.c_int, [HP, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "nadm_sum_rows": (C.c_int, [vp, i64, i64, vp, vp]),
         "nadm_supervised_ce": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp]),
+        "nadm_class_sums": (C.c_int, [vp, i64, i64, i64, vp, C.POINTER(i64), i32, vp, vp]),
         "nadm_encode_bwd": (C.c_int, [vp, i64, vp, i32, i64, vp, vp, i32, vp, i32, vp]),
         "nadm_dz_image_bytes": (C.c_int64, [i32]),
         "nadm_dz_image_tile_bytes": (C.c_int64, []),

@@ -40,8 +40,14 @@ def parse_train_args(argv):
     p.add_argument("--save_dir", required=True, type=str)
     p.add_argument("--data_path", required=True, type=str)
     p.add_argument("--name", required=True, type=str)
-    p.add_argument("--supervised_loss_weight", type=float, default=100)
+    p.add_argument("--supervised_loss_weight", type=float, default=100,
+                   help="weight of the supervised term (default 100, the reference's); lower it when unlabelled samples come out "
+                        "with a single ancestry")
     p.add_argument("--pops_path", type=str, default="")
+    p.add_argument("--unlabelled", type=str, default="-", metavar="TOKEN",
+                   help="line of --pops_path that marks a sample WITHOUT a label (default '-', the convention of ADMIXTURE's .pop "
+                        "files): such samples train the reconstruction only and get their Q like any other.  A population can "
+                        "therefore not be named TOKEN itself; pass another token if one is literally named '-'")
     p.add_argument("--n_components", type=int, default=8)
     p.add_argument("--num_gpus", type=int, default=1)
     p.add_argument("--threads", type=int, default=1,
@@ -107,7 +113,8 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
     K = args.k
     Ps, Qs, model = train(args.epochs, args.batch_size, args.learning_rate, K, args.seed, data, device, num_gpus, args.hidden_size,
                           master, V, pops, args.min_k, args.max_k, args.n_components, parallelism=args.parallelism,
-                          host_threads=args.threads, gmm=args.gmm, precision=args.precision)
+                          host_threads=args.threads, gmm=args.gmm, precision=args.precision,
+                          unlabelled=None if pops is None else (args.unlabelled,), supervised_loss_weight=args.supervised_loss_weight)
     if master:
         save_model(model, args.name, args.save_dir)
         write_outputs(Qs, args.name, K, args.min_k, args.max_k, args.save_dir, Ps)

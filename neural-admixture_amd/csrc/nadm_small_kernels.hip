@@ -1021,6 +1021,8 @@ __global__ __launch_bounds__(256) void bed_flip_kernel(uint8_t* __restrict__ out
 //   loss_i = logsumexp(q_i) - q_i[y_i],  d/dq_ij = softmax(q_i)_j - [j == y_i]
 // The gradient is added to chunk 0 of head 0's dQ slab (mlp_bwd sums the chunks), the weighted loss
 // goes to one slot of the losspart array.  Fixed order -> deterministic.
+// A row without a label (y == NADM_LABEL_NONE) is skipped: nothing added to its dQ, nothing to the loss --
+// CrossEntropyLoss(reduction='sum')'s ignored target; the sum is not renormalised.
 // =================================================================================================
 __global__ __launch_bounds__(256) void supervised_ce_kernel(const float* __restrict__ Q, int SP, int k, int kp,
                                                            const int32_t* __restrict__ labels, const int32_t* __restrict__ idx,
@@ -1030,6 +1032,7 @@ __global__ __launch_bounds__(256) void supervised_ce_kernel(const float* __restr
     for (int i = tid; i < b; i += 256) {
         const float* q = Q + (int64_t)i * SP;
         const int y = labels[idx ? idx[i] : i];
+        if (y == NADM_LABEL_NONE) continue;
         float qm = q[0];
         for (int j = 1; j < k; ++j) qm = fmaxf(qm, q[j]);
         float se = 0.f;
@@ -1049,6 +1052,52 @@ __global__ __launch_bounds__(256) void supervised_ce_kernel(const float* __restr
     if ((tid & 63) == 0) s_l[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) *loss_slot = (float)((double)weight * ((s_l[0] + s_l[1]) + (s_l[2] + s_l[3])));
+}
+
+// =================================================================================================
+// class_sums: sums[c][m] += sum over the rows of class c of the raw 2-bit code of SNP m (0, 1, 2, missing 3) -- the numerator of
+// the supervised P init (train.py:82) straight from the packed matrix, one pass over it.
+// grid (256-word tiles of a row, classes, row slices of a class).  idx lists the rows grouped by class, class c owning
+// idx[start[c] .. start[c+1]); slice z of Z takes the z-th Z-th of that range.  A thread owns ONE 32-bit word of the row (16 SNPs:
+// a wave reads 256 contiguous bytes of each row), splits it into four words of byte lanes (lane B of split i = SNP 4B + i) and adds
+// up to 80 rows there (80 * 3 < 256) before widening into 16 uint32 registers.  The row index is uniform over the block.  Slices of
+// one class share their output words, and a later call adds to what an earlier one left: atomicAdd throughout -- integers, so the
+// result does not depend on the order.  Fields at SNP >= M (the ragged last word, whatever the pad holds) are never written, and
+// words past ceil(M/16) -- the ld padding -- never read.
+// =================================================================================================
+struct ClassStarts { int64_t s[NADM_MAX_K + 1]; };
+
+__global__ __launch_bounds__(256) void class_sums_kernel(const uint32_t* __restrict__ xw, int64_t ldw, int64_t rows, int64_t M,
+                                                         const int32_t* __restrict__ idx, ClassStarts cs, uint32_t* __restrict__ sums) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= (M + 15) / 16) return;
+    const int c = blockIdx.y;
+    const int64_t len = cs.s[c + 1] - cs.s[c];
+    int64_t j = cs.s[c] + len * blockIdx.z / gridDim.z;
+    const int64_t j1 = cs.s[c] + len * (blockIdx.z + 1) / gridDim.z;
+    if (j >= j1) return;
+    uint32_t acc[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) acc[s] = 0u;
+    while (j < j1) {
+        const int64_t je = j + 80 < j1 ? j + 80 : j1;
+        uint32_t lane[4] = {0u, 0u, 0u, 0u};
+#pragma unroll 8
+        for (; j < je; ++j) {
+            const int64_t r = idx[j];
+            const bool inside = r >= 0 && r < rows;              // never read outside the matrix (branch-free: the loads of a trip stay in flight together)
+            const uint32_t x = xw[(inside ? r : 0) * ldw + w];
+            const uint32_t v = inside ? x : 0u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) lane[i] += (v >> (2 * i)) & 0x03030303u;
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) acc[s] += (lane[s & 3] >> (8 * (s >> 2))) & 0xFFu;
+    }
+    uint32_t* out = sums + (int64_t)c * M + w * 16;
+#pragma unroll
+    for (int s = 0; s < 16; ++s)
+        if (w * 16 + s < M && acc[s] != 0u) atomicAdd(out + s, acc[s]);
 }
 
 // =================================================================================================
@@ -1661,6 +1710,35 @@ extern "C" int nadm_supervised_ce(const float* Q, int32_t SP, int32_t k, int32_t
     if (n_classes != k) return fail("nadm_supervised_ce: number of classes must equal K");   // train.py:79
     hipLaunchKernelGGL(supervised_ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, Q, SP, k, kp, labels, idx, b, weight, dqpart0, loss_slot);
     return check_launch("supervised_ce");
+}
+
+extern "C" int nadm_class_sums(const uint8_t* xp, int64_t ld, int64_t rows, int64_t M, const int32_t* idx, const int64_t* class_start,
+                               int32_t n_classes, uint32_t* sums, void* stream) {
+    if (!xp || !class_start || !sums) return fail("nadm_class_sums: null pointer");
+    if (n_classes < 1 || n_classes > NADM_MAX_K) return fail("nadm_class_sums: need 1 <= n_classes <= NADM_MAX_K");
+    if (rows <= 0 || M <= 0) return fail("nadm_class_sums: empty matrix");
+    if (rows > 0xFFFFFFFFll / 3) return fail("nadm_class_sums: 3 * rows must fit in 32 bits");
+    if (ld % 4 != 0 || ld * 4 < M || ((uintptr_t)xp & 3) != 0) return fail("nadm_class_sums: rows must be whole 32-bit words: ld a multiple of 4 and >= ceil(M/4), xp 4-byte aligned");
+    ClassStarts cs;
+    int64_t longest = 0;
+    if (class_start[0] < 0) return fail("nadm_class_sums: class_start must start at >= 0");
+    for (int c = 0; c < n_classes; ++c) {
+        if (class_start[c + 1] < class_start[c]) return fail("nadm_class_sums: class_start must not decrease");
+        if (class_start[c + 1] - class_start[c] > longest) longest = class_start[c + 1] - class_start[c];
+    }
+    if (class_start[n_classes] - class_start[0] > rows) return fail("nadm_class_sums: more listed rows than rows");
+    if (longest == 0) return 0;                                   // no labelled row: nothing to add
+    if (!idx) return fail("nadm_class_sums: null pointer");
+    for (int c = 0; c <= NADM_MAX_K; ++c) cs.s[c] = class_start[c < n_classes ? c : n_classes];
+    const int64_t tiles = ((M + 15) / 16 + 255) / 256;
+    if (tiles > 0x7FFFFFFFll) return fail("nadm_class_sums: M too large for one launch");
+    // row slices: enough blocks to fill the chip (2048), none shorter than one 80-row trip of the longest class
+    int64_t slices = (2048 + tiles * n_classes - 1) / (tiles * n_classes);
+    if (slices > (longest + 79) / 80) slices = (longest + 79) / 80;
+    if (slices > 65535) slices = 65535;
+    dim3 grid((unsigned)tiles, (unsigned)n_classes, (unsigned)slices), block(256);
+    hipLaunchKernelGGL(class_sums_kernel, grid, block, 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(xp), ld / 4, rows, M, idx, cs, sums);
+    return check_launch("class_sums");
 }
 
 // VCF text -> genotype codes, the semantics of the reference's reader (src/snp_reader.py:73-87): scikit-allel's

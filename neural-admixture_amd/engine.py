@@ -28,7 +28,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import lib, check, ptr, PlanDesc, MODE_SINGLE, MODE_DP, MODE_SNP, PRECISION_HIGHEST, PRECISION_MEDIUM, T_NAMES, MAX_BUCKETS
+from ._lib import lib, check, ptr, PlanDesc, MODE_SINGLE, MODE_DP, MODE_SNP, PRECISION_HIGHEST, PRECISION_MEDIUM, T_NAMES, MAX_BUCKETS, LABEL_NONE
 from .layout import ModelLayout
 
 _f32 = torch.float32
@@ -280,13 +280,14 @@ class Engine:
         self.set_packed(xp)
 
     def set_labels(self, labels, n_classes: int, weight: float = 100.0) -> None:
-        """Supervised mode (neural_admixture.py:460-474): class index per RESIDENT row (same order as xp)."""
+        """Supervised mode (neural_admixture.py:460-474): class index per RESIDENT row (same order as xp); -1 (NADM_LABEL_NONE)
+        marks a row without a label, which stays out of the supervised term."""
         lab = torch.as_tensor(np.asarray(labels), dtype=torch.int32)
         if lab.dim() != 1 or (self.xp is not None and lab.numel() != self.xp.shape[0]):
             raise RuntimeError("labels must be one class index per resident genotype row")
         if len(self.lay.ks) != 1 or int(n_classes) != self.lay.ks[0]:
             raise RuntimeError(f"supervised mode needs a single head with K == number of classes ({n_classes})")
-        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= int(n_classes)):
+        if lab.numel() and (int(lab.min()) < LABEL_NONE or int(lab.max()) >= int(n_classes)):
             raise RuntimeError("label out of range")
         self.labels, self.n_classes, self.sup_weight = lab.to(self.device), int(n_classes), float(weight)
         if self._plan is not None:

@@ -129,26 +129,63 @@ def _gmm_means_parallel(X_pca: np.ndarray, ks, seed: int):
                 p.wait()
 
 
-def supervised_init(data_np, pops, K: int):
+def class_sums_gpu(data, y: np.ndarray, K: int, device: torch.device, chunk_rows: int = 4096) -> np.ndarray:
+    """uint32 [K, M]: per class the exact sum of the raw 2-bit codes (0, 1, 2, missing 3) over the rows labelled with it, rows with
+    y == -1 left out -- computed by nadm_class_sums from 2-bit packed rows.  A matrix that already lives on the GPU (a
+    PackedGenotypes read with keep_on_device) is summed where it is, in one call; anything else is packed on the host and streamed
+    ``chunk_rows`` at a time, the calls adding into the same array."""
+    import ctypes as C
+    from ._lib import lib, check, ptr
+    from .layout import ModelLayout
+    from .io import packed_chunks
+    N, M = data.shape
+    resident = hasattr(data, "packed") and data.packed.is_cuda
+    ld = int(data.packed.shape[1]) if hasattr(data, "packed") else ModelLayout.row_stride(M)
+    sums = torch.zeros((K, M), dtype=torch.int32, device=device)           # (the bits of uint32: read back through a view)
+    st = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.device(device):
+        for s, e, pk in packed_chunks(data, ld, N if resident else chunk_rows):
+            yb = y[s:e]
+            order = np.argsort(yb, kind="stable")                         # rows grouped by class, -1 first
+            start = np.searchsorted(yb[order], np.arange(K + 1)).astype(np.int64)
+            if start[K] == start[0]:
+                continue                                                   # no labelled row in this chunk
+            idx = torch.from_numpy(order.astype(np.int32)).to(device)
+            xp = pk.to(device).contiguous()
+            check(lib.nadm_class_sums(ptr(xp), ld, e - s, M, ptr(idx), start.ctypes.data_as(C.POINTER(C.c_int64)), K, ptr(sums), st),
+                  "class_sums")                                            # (xp / idx go back to the allocator in stream order)
+    return sums.cpu().numpy().view(np.uint32)
+
+
+def supervised_init(data_np, pops, K: int, unlabelled=(), device: Optional[torch.device] = None):
     """Supervised mode (train.py:74-83): population names -> class indices in sorted order, and
     P_init [K,M] = per-class mean of the RAW codes (0,1,2, missing 3; not halved, not clipped -- the first
-    restrict_P brings it into [0,1]).  ``data_np``: uint8 [N,M] or an io.PackedGenotypes."""
-    names = sorted(np.unique([a for a in pops]))
+    restrict_P brings it into [0,1]).  ``data_np``: uint8 [N,M] or an io.PackedGenotypes.
+    ``unlabelled``: names in ``pops`` that stand for "no label" (one string or a collection; ADMIXTURE's .pop files use "-").
+    Those samples get y = -1, the classes are the sorted unique REMAINING names, and a class mean runs over the rows labelled with
+    it only -- the semi-supervised case the reference does not take.  With a GPU ``device`` the per-class sums come from the packed
+    matrix (class_sums_gpu), else from the host loop; both are exact integers and share the float64 division, so they give the
+    same bits."""
+    skip = {unlabelled} if isinstance(unlabelled, str) else set(unlabelled)
+    names = sorted(np.unique([a for a in pops if a not in skip]))
     if K is None or len(names) != K:
         raise AssertionError(f"Number of ancestries in training ground truth ({len(names)}) is not equal to the value of K ({K})")
     lut = {a: i for i, a in enumerate(names)}
-    y = np.asarray([lut[a] for a in pops], dtype=np.int64)
+    y = np.asarray([-1 if a in skip else lut[a] for a in pops], dtype=np.int64)
     N, M = data_np.shape
     if len(y) != N:
         raise RuntimeError("pops must hold one population label per sample")
-    rows = data_np.unpack_rows if hasattr(data_np, "unpack_rows") else (lambda s, e: data_np[s:e])
-    sums = np.zeros((K, M), dtype=np.float64)
-    for i in range(0, N, 1024):
-        blk, yb = rows(i, min(N, i + 1024)), y[i:i + 1024]
-        for k in range(K):
-            if np.any(yb == k):
-                sums[k] += blk[yb == k].sum(axis=0, dtype=np.float64)
-    P = (sums / np.bincount(y, minlength=K)[:, None]).astype(np.float32)
+    if device is not None and device.type == "cuda":
+        sums = class_sums_gpu(data_np, y, K, device).astype(np.float64)
+    else:
+        rows = data_np.unpack_rows if hasattr(data_np, "unpack_rows") else (lambda s, e: data_np[s:e])
+        sums = np.zeros((K, M), dtype=np.float64)
+        for i in range(0, N, 1024):
+            blk, yb = rows(i, min(N, i + 1024)), y[i:i + 1024]
+            for k in range(K):
+                if np.any(yb == k):
+                    sums[k] += blk[yb == k].sum(axis=0, dtype=np.float64)
+    P = (sums / np.bincount(y[y >= 0], minlength=K)[:, None]).astype(np.float32)
     return y, P
 
 
@@ -184,23 +221,31 @@ def capped_host_threads(limit: int = 4):
 
 def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
           num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
-          n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto", precision: str = "highest"):
+          n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto", precision: str = "highest",
+          unlabelled=None, supervised_loss_weight: float = 100.0):
     """The reference's boundary function (see the module docstring and _train).  The host thread pools (torch intra-op, BLAS,
     OpenMP) are capped at ``host_threads`` while it runs -- the reference's CLI does that with --threads (entry.py:138-146), and
     this package's CLI passes its --threads here; the epoch loop itself always runs with torch's pool at 1 (model.py).
     ``gmm`` (keyword, CLI --gmm): who fits the decoder-init mixture (gmm_p_init's ``fit``): "sklearn" is the reference's own call.
     ``precision`` (keyword, CLI --precision): the matmul precision of the training step, "highest" (fp32-class products, the default)
-    or "medium" (bf16-class: the reference's torch.set_float32_matmul_precision('medium'))."""
+    or "medium" (bf16-class: the reference's torch.set_float32_matmul_precision('medium')).
+    ``unlabelled`` (keyword, CLI --unlabelled): names in ``pops`` that mean "this sample has no label" (one string or a collection;
+    None, the default: every entry is a class name, the reference's contract).  Such samples take part in the reconstruction loss
+    like any other and stay out of the supervised term and of the class means of the decoder init (supervised_init).
+    ``supervised_loss_weight`` (keyword, CLI --supervised_loss_weight): the weight of the supervised term, 100 like the reference's
+    default."""
     if precision not in PRECISIONS:
         raise ValueError("precision must be 'highest' or 'medium'")
     with capped_host_threads(max(1, int(host_threads))):
         return _train(epochs, batch_size, learning_rate, K, seed, data, device, num_gpus, hidden_size, master, V, pops, min_k, max_k,
-                      n_components, parallelism=parallelism, gmm=gmm, precision=precision)
+                      n_components, parallelism=parallelism, gmm=gmm, precision=precision, unlabelled=unlabelled,
+                      supervised_loss_weight=supervised_loss_weight)
 
 
 def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
            num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
-           n_components: int = None, *, parallelism: str = "dp", gmm: str = "auto", precision: str = "highest"):
+           n_components: int = None, *, parallelism: str = "dp", gmm: str = "auto", precision: str = "highest", unlabelled=None,
+           supervised_loss_weight: float = 100.0):
     """See module docstring.  ``data`` uint8 [N,M] CPU tensor (or an ``io.PackedGenotypes``, e.g. from
     ``io.read_bed_packed``); ``V`` numpy [C,M] (RSVD output,
     svd.py:83); returns Ps (list of [M,k] float32), Qs (list of [N,k] float32), model.
@@ -224,7 +269,11 @@ def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int
         log.info("")
         log.info("    Running Supervised Mode...")
         log.info("")
-        y_num, P = supervised_init(data if hasattr(data, "unpack_rows") else data.numpy(), pops, K)
+        y_num, P = supervised_init(data if hasattr(data, "unpack_rows") else data.numpy(), pops, K,
+                                   unlabelled=() if unlabelled is None else unlabelled, device=device)
+        if (y_num < 0).any():
+            log.info(f"    Labelled samples: {int((y_num >= 0).sum())}, unlabelled samples: {int((y_num < 0).sum())}.")
+            log.info("")
     if dist.is_available() and dist.is_initialized():
         dist.barrier()
     if num_gpus > 1 and dist.is_available() and dist.is_initialized():
@@ -255,7 +304,7 @@ def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int
     if master and precision != "highest":
         log.info(f"    Matmul precision: {precision} (bf16-class products in the genotype passes).")
     model = NeuralAdmixture(K, epochs, batch_size, learning_rate, device, seed, num_gpus, master, None, min_k, max_k,
-                            parallelism=parallelism, precision=precision)
+                            supervised_loss_weight=supervised_loss_weight, parallelism=parallelism, precision=precision)
     Qs, Ps, raw = model.launch_training(P_init, data, hidden_size, Vt.shape[1], Vt, M, N, pops)
 
     if master:
