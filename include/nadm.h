@@ -43,7 +43,7 @@ extern "C" {
 #define NADM_MAX_K 64
 #define NADM_MAX_BUCKETS 8
 #define NADM_MAX_P2_SLICES 8   /* sample slices of pass 2 (nadm_decode_bce_sliced) */
-#define NADM_ABI_VERSION 14  /* 14: nadm_clock_probe; new symbols only, same version: nadm_plan_set_precision / nadm_plan_precision (NADM_PRECISION_*), nadm_class_sums + NADM_LABEL_NONE (labels in [-1, k)); 13: pass 3 in sample slices (nadm_encode_bwd_sliced, nadm_encode_slices(_max), nadm_encode_slab_floats, nadm_encode_bwd_chunks, nadm_plan_desc_t.p3_slab / p3_cnt); 12: nadm_test_force_slices / nadm_test_force_generic_mlp exist in the test build only (-DNADM_TEST_HOOKS), nadm_calib_clock / nadm_wall_clock_khz; 11: nadm_gmm_fit_means_dev, nadm_loglik_blocks counts 8 row slices per 1024-SNP block, nadm_decode_bce_sliced / nadm_decode_slices / nadm_decode_slab_floats / nadm_test_force_slices + nadm_plan_desc_t.p2_slab / p2_cnt (pass 2 in sample slices when the SNP chunks alone do not fill the chip); 10: message B of the sample-sharded step in SNP-range buckets (nadm_flat_layout takes n_buckets, nadm_flat_layout_t.bkt_*, nadm_plan_desc_t.n_buckets / p3_whole / comm_a / debug, nadm_encode_fwd_part, nadm_plan_bucket_ms), nadm_comm_t.async_error, nadm_comm_rccl_probe, nadm_comm_rccl with a watchdog (timeout_ms), a failed step poisons its plan; 9: nadm_step / nadm_plan_* / nadm_comm_* / nadm_flat_layout (the step as one call, sharded optimizer), nadm_test_force_generic_mlp; 8: nadm_dz_image(_bytes), nadm_mlp_bwd_image; nadm_encode_bwd, nadm_encode_bwd_step, nadm_pca_project_t take the operand image of dZ / Y; 7: nadm_encode_fwd_step, nadm_sum_rows, dqpart of nadm_mlp_bwd is float* (folded in place); 6: nadm_mlp_fwd_images, nadm_decode_bce_images, nadm_q_image_bytes, nadm_encode_fwd_small; 5: nadm_adam_t.when, nadm_adam2, with_loss bit 1; 4: nadm_decode_bce_step, nadm_encode_bwd_step (nadm_adam_t, nadm_mlp_weights_t), nadm_small_grads; 3: nadm_decode_bce_gather; 2: nadm_mlp_bwd_weights, nadm_supervised_ce, nadm_pca_project(_t), nadm_loglik, nadm_savetxt_f32, nadm_decode_chunk_snps; grad_small of nadm_mlp_bwd may be NULL */
+#define NADM_ABI_VERSION 14  /* 14: nadm_clock_probe; new symbols only, same version: nadm_plan_set_precision / nadm_plan_precision (NADM_PRECISION_*), nadm_class_sums + NADM_LABEL_NONE (labels in [-1, k)), nadm_project_q / nadm_project_scratch_floats (projection: Q refined against a fixed P); 13: pass 3 in sample slices (nadm_encode_bwd_sliced, nadm_encode_slices(_max), nadm_encode_slab_floats, nadm_encode_bwd_chunks, nadm_plan_desc_t.p3_slab / p3_cnt); 12: nadm_test_force_slices / nadm_test_force_generic_mlp exist in the test build only (-DNADM_TEST_HOOKS), nadm_calib_clock / nadm_wall_clock_khz; 11: nadm_gmm_fit_means_dev, nadm_loglik_blocks counts 8 row slices per 1024-SNP block, nadm_decode_bce_sliced / nadm_decode_slices / nadm_decode_slab_floats / nadm_test_force_slices + nadm_plan_desc_t.p2_slab / p2_cnt (pass 2 in sample slices when the SNP chunks alone do not fill the chip); 10: message B of the sample-sharded step in SNP-range buckets (nadm_flat_layout takes n_buckets, nadm_flat_layout_t.bkt_*, nadm_plan_desc_t.n_buckets / p3_whole / comm_a / debug, nadm_encode_fwd_part, nadm_plan_bucket_ms), nadm_comm_t.async_error, nadm_comm_rccl_probe, nadm_comm_rccl with a watchdog (timeout_ms), a failed step poisons its plan; 9: nadm_step / nadm_plan_* / nadm_comm_* / nadm_flat_layout (the step as one call, sharded optimizer), nadm_test_force_generic_mlp; 8: nadm_dz_image(_bytes), nadm_mlp_bwd_image; nadm_encode_bwd, nadm_encode_bwd_step, nadm_pca_project_t take the operand image of dZ / Y; 7: nadm_encode_fwd_step, nadm_sum_rows, dqpart of nadm_mlp_bwd is float* (folded in place); 6: nadm_mlp_fwd_images, nadm_decode_bce_images, nadm_q_image_bytes, nadm_encode_fwd_small; 5: nadm_adam_t.when, nadm_adam2, with_loss bit 1; 4: nadm_decode_bce_step, nadm_encode_bwd_step (nadm_adam_t, nadm_mlp_weights_t), nadm_small_grads; 3: nadm_decode_bce_gather; 2: nadm_mlp_bwd_weights, nadm_supervised_ce, nadm_pca_project(_t), nadm_loglik, nadm_savetxt_f32, nadm_decode_chunk_snps; grad_small of nadm_mlp_bwd may be NULL */
 
 /* Head table shared by the MLP entry points (mirror of NeuralEncoder/NeuralDecoder's ks list,
  * neural_admixture.py:27-29,66-76). Offsets are element offsets into the `small` flat buffer. */
@@ -526,6 +526,33 @@ void nadm_test_force_generic_mlp(int32_t on);
 int64_t nadm_loglik_blocks(int64_t M);
 int nadm_loglik(const uint8_t* xp, int64_t ld, int64_t rows, int64_t M, const float* P, const float* Q, int32_t K,
                 int32_t q_stride, double eps, double* partial, void* stream);
+
+/* ---- projection: refine Q against a FIXED P with masked EM steps ------------------------------------------------------------
+ * What ADMIXTURE-family tools call projection (ADMIXTURE -P): P stays as trained, every sample's Q row is fitted to its OWN
+ * observed calls by maximum likelihood.  One call = one EM step of the binomial admixture model (the FRAPPE / ADMIXTURE
+ * update: no step size, keeps sum(q) = 1, never lowers ll while the clip is inactive) for the rows idx[0..b) (idx == NULL:
+ * rows 0..b; any order, duplicates allowed) and ONE head of k columns.  Codes g in {0, 1, 2} are observed, 3 is missing, only
+ * SNPs j < M count:
+ *     r_j  = clip( sum_k q_k p_jk , eps, 1 - eps )
+ *     a_k  = sum over observed j of [ p_jk g_j / r_j  +  (1 - p_jk) (2 - g_j) / (1 - r_j) ]
+ *     n    = number of observed j
+ *     ll   = sum over observed j of [ g_j log r_j + (2 - g_j) log(1 - r_j) ]              (at the INPUT q)
+ *     q'_k = q_k a_k / (2n);   q''_k = max(q'_k, qmin);   q_out = q'' / sum_k q''_k
+ *     n == 0:  q_out = q_in exactly, ll = 0
+ * P [M, kp] (kp = nadm_pad_k(k), pad cols 0); Qin / Qout rows of b with row stride q_stride (a multiple of 4, >= kp; Qout may
+ * be Qin; padded columns k >= K come out 0); eps in [1e-9, 0.5) (the log-likelihood report's is 1e-6), qmin in [0, 1) (1e-6);
+ * loglik double [b] and nobs int32 [b] may be NULL -- loglik == NULL skips the logarithms, the expensive part of a step.
+ * scratch: nadm_project_scratch_floats(b, M, kp) floats.  xp, P, Qin, Qout, scratch 16-byte aligned; ld % 16 == 0, ld < 2^32.
+ * A missing call and a SNP >= M enter every sum as exactly +0.0f (a sample's result does not depend on P where its call is
+ * missing, nor on the pad bits of its last byte); sums are fp32 within a 256-SNP chunk, the chunks' partials are added in
+ * float64 in a fixed order that depends on (M, kp) alone (a_k: contiguous ranges of chunks, each in chunk order, then the
+ * ranges in order; n, ll: strided over the lanes, then a fixed butterfly); no floating-point atomics: the same inputs give
+ * the same bits.  kp <= 16 is the fast path, wider
+ * heads run the same kernel with P staged in pieces.  Every refusal is reported before anything is launched. */
+int64_t nadm_project_scratch_floats(int32_t b, int64_t M, int32_t kp);
+int nadm_project_q(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                   const float* P, int32_t k, int32_t kp, const float* Qin, float* Qout, int32_t q_stride,
+                   float eps, float qmin, double* loglik, int32_t* nobs, float* scratch, void* stream);
 
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,

@@ -76,6 +76,12 @@ def parse_infer_args(argv):
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--num_gpus", type=int, default=1)
     p.add_argument("--threads", type=int, default=1)
+    p.add_argument("--refine", type=int, default=0, metavar="N",
+                   help="after the encoder pass, refine every sample's Q with up to N masked EM steps against the trained allele "
+                        "frequencies {save_dir}/{name}.{K}.P held fixed (projection: only a sample's observed calls count). "
+                        "0 (default): the encoder's Q as it is")
+    p.add_argument("--refine_tol", type=float, default=1e-4,
+                   help="stop refining a batch once no entry of Q moves by this much in a step")
     _add_precision(p)
     return p.parse_args(argv)
 
@@ -168,7 +174,13 @@ def main(argv=None):
     from .io import write_outputs
     with open(f"{args.save_dir}/{args.name}_config.json") as fb:
         cfg = json.load(fb)
+    Ps = None
+    if args.refine > 0:                                    # the training run's {name}.{k}.P, looked for before anything is loaded
+        from .project import find_P_files, read_P_files
+        P_paths = find_P_files(args.save_dir, args.name, cfg["ks"])
     sd = torch.load(f"{args.save_dir}/{args.name}.pt", map_location="cpu", weights_only=True)
+    if args.refine > 0:                                    # one row per SNP of the model: V is [M, num_features]
+        Ps = read_P_files(P_paths, cfg["ks"], int(sd["V"].shape[0]))
     model = Q_P(int(cfg["hidden_size"]), int(cfg["num_features"]), ks_list=cfg["ks"], is_train=False)
     if args.precision != "highest":
         log.info(f"    Matmul precision: {args.precision} (bf16-class products in the genotype passes).")
@@ -178,10 +190,23 @@ def main(argv=None):
     eng.pack_from_host(data)
     idx = torch.arange(data.N, dtype=torch.int32, device=eng.device)
     outs = [[] for _ in cfg["ks"]]
+    if Ps is not None:
+        for h, P_MK in enumerate(Ps):
+            eng.load_P(h, P_MK)
+        ll0 = ll1 = 0.0
     for s in range(0, data.N, args.batch_size):
         bb = min(args.batch_size, data.N - s)
-        for h, q in enumerate(eng.infer_q(idx[s:s + bb], bb)):
+        qs = eng.infer_q(idx[s:s + bb], bb)
+        if Ps is not None:                                 # projection: the encoder's Q is the start of the masked EM steps
+            _, lls, _ = eng.project_q(idx[s:s + bb], bb, q0=qs, iters=0, with_loglik=True)
+            ll0 += float(sum(ll.sum() for ll in lls))
+            qs, lls, _ = eng.project_q(idx[s:s + bb], bb, q0=qs, iters=args.refine, tol=args.refine_tol, with_loglik=True)
+            ll1 += float(sum(ll.sum() for ll in lls))
+        for h, q in enumerate(qs):
             outs[h].append(q.cpu().numpy())
+    if Ps is not None:
+        log.info(f"    Log-likelihood of the observed calls before refinement: {ll0:.3f}")
+        log.info(f"    Log-likelihood of the observed calls after refinement:  {ll1:.3f}")
     Qs = [np.concatenate(o, axis=0) for o in outs]
     K = cfg["ks"][0] if len(cfg["ks"]) == 1 else None
     write_outputs(Qs, args.out_name, K, cfg["ks"][0], cfg["ks"][-1], args.save_dir)

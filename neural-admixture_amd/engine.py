@@ -116,6 +116,7 @@ class Engine:
         self._qimg_b = self._dzimg_b = -1
         self._dz_last_b = 0
         self._xg_key = None
+        self.project_iters = 0                          # EM steps the last project_q call ran (fewer than its iters: the early stop)
         self.xp: Optional[torch.Tensor] = None          # packed genotypes [rows, ld]
         self.labels: Optional[torch.Tensor] = None      # int32 [rows], supervised mode only
         self.n_classes, self.sup_weight = 0, 0.0
@@ -514,6 +515,44 @@ class Engine:
             self.forward(idx, b)
         Q = self._Q[: b * L.SP].view(b, L.SP)
         return [Q[:, L.qoff[h]: L.qoff[h] + k].clone() for h, k in enumerate(L.ks)]
+
+    # ------------------------------------------------------------------ projection (Q refined against the engine's own P)
+    def load_P(self, h: int, P_MK) -> None:
+        """Head h's allele frequencies from a host (or device) matrix [M, k_h] -- for an engine built by Q_P.load_state_dict, which
+        carries the encoder only (the reference's .pt has no decoders; the training run wrote them as {name}.{k}.P)."""
+        L = self.lay
+        Pt = torch.as_tensor(np.asarray(P_MK) if not isinstance(P_MK, torch.Tensor) else P_MK).to(_f32)
+        if tuple(Pt.shape) != (L.M, L.ks[h]):
+            raise RuntimeError(f"load_P: head {h} needs a [{L.M}, {L.ks[h]}] matrix")
+        self.sync()
+        self.pflat[L.off_v + L.p_off[h]: L.off_v + L.p_off[h] + L.M * L.kp[h]].view(L.M, L.kp[h])[:, : L.ks[h]].copy_(Pt.to(self.device))
+        self.invalidate_q()                              # (P was edited: the loss path clamps until the next restrict_P)
+
+    def project_q(self, idx: torch.Tensor, b: int, q0: Optional[Sequence[torch.Tensor]] = None, iters: int = 20, tol: float = 1e-4,
+                  with_loglik: bool = False):
+        """Per head the [b, k] ancestry fractions of the batch rows idx after ``iters`` masked EM steps against the engine's P held
+        fixed (project.py; include/nadm.h, nadm_project_q): only the OBSERVED calls of a sample count, where the encoder reads a
+        missing call as genotype 0.  ``q0``: per-head start [b, k] (default: ``infer_q``'s output); stops early once
+        max |q_out - q_in| < tol over the batch and heads.  ``with_loglik``: also per head the log-likelihood per sample at the
+        returned Q (float64 [b]) and the number of observed calls (int32 [b]) -> (Qs, lls, nobs).  The number of steps the call ran
+        is left in ``self.project_iters`` (0 before the first call; below ``iters`` when the early stop triggered)."""
+        from . import project
+        if self.mode != "single" or self.world != 1:
+            raise NotImplementedError("Engine.project_q is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
+                                      "P; project with project.project_q on one GPU from the written .P file instead")
+        if self._plan is None:
+            raise RuntimeError("Engine.project_q needs the HIP engine (no CPU fallback)")
+        L = self.lay
+        if q0 is None:
+            q0 = self.infer_q(idx, b)
+        if len(q0) != len(L.ks):
+            raise RuntimeError("q0 must hold one [b, k] matrix per head")
+        big = self.big                                   # (settles what the last step left to the next one)
+        Pps = [big[L.p_off[h]: L.p_off[h] + L.M * L.kp[h]].view(L.M, L.kp[h]) for h in range(len(L.ks))]
+        q0p = [project.pad_Q(q, b, k, L.kp[h], self.device) for h, (q, k) in enumerate(zip(q0, L.ks))]
+        Qs, lls, nobs, self.project_iters = project.refine_heads(self.xp, L.M, idx, b, Pps, L.ks, q0p, iters, tol, with_loglik=with_loglik)
+        Qs = [q[:, :k].clone() for q, k in zip(Qs, L.ks)]
+        return (Qs, lls, nobs) if with_loglik else Qs
 
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
