@@ -14,8 +14,6 @@
 #include "nadm_common.h"
 #include "../../include/nadm.h"
 #include "nadm_host.h"
-extern "C" int nadm_mlp_bwd_weight_parts(const nadm_heads_t* hd, int32_t b, const float* Zn, const float* H, const float* dL,
-                                         const float* dHpre, const float* dgp, float* small_part, void* stream);
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
@@ -1979,19 +1977,11 @@ extern "C" int nadm_decode_bce_images(const uint8_t* xp, int64_t ld, const int32
 }
 
 // ---- pass 2 with the batch's sample tiles dealt to n_slices blocks per SNP chunk (see decode_bce_bf16_kernel)
-#ifdef NADM_TEST_HOOKS          // the test build only (csrc/build.sh -> libnadm_testhooks.so): the shipping library has no way to override the rule below
-static std::atomic<int> g_force_slices{0};
-extern "C" void nadm_test_force_slices(int32_t n) { g_force_slices.store(n < 0 ? 0 : (n > NADM_MAX_P2_SLICES ? NADM_MAX_P2_SLICES : n)); }
-#endif
-
 extern "C" int32_t nadm_decode_slices(int32_t b, int64_t M, int32_t kp) {
     if (kp > 16 || b <= 0 || M <= 0) return 1;
     const int64_t chunks = (M + mf_chunk_snps(8) - 1) / mf_chunk_snps(8);
     const int tiles = (b + NADM_BF_TS - 1) / NADM_BF_TS;
-    int s = 0;
-#ifdef NADM_TEST_HOOKS
-    s = g_force_slices.load();
-#endif
+    int s = hook_p2_slices();                                       // 0 (always, in the shipping library): the rule below
     if (s == 0) {
         // Measured (profiles/r05_ablations.txt item 11): below ~130k SNPs pass 2 is bound by the serial chain of ONE block -- its prologue
         // (P rows into operands, ~1.5 tile-times) + 13 tiles at b = 800 = 49 us whether 98 or 196 blocks run -- not by the chip; slices of
@@ -2120,7 +2110,7 @@ static int encode_bwd_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, in
     }
     if (check_launch("encode_bwd")) return 1;
     if (ad.m && launch_adam_range(Vrw, dV, ad, M * CP, st, 0)) return 1;  // fp32 variants of pass 3: stand-alone update
-    return mw ? nadm_mlp_bwd_weight_parts(mw->hd, b, mw->Zn, mw->H, mw->dL, mw->dHpre, mw->dgp, mw->small_part, stream) : 0;
+    return mw ? mlp_bwd_weight_parts(mw->hd, b, mw->Zn, mw->H, mw->dL, mw->dHpre, mw->dgp, mw->small_part, stream) : 0;
 }
 
 extern "C" int nadm_encode_bwd_step(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
@@ -2135,19 +2125,11 @@ extern "C" int nadm_encode_bwd_step(const uint8_t* xp, int64_t ld, const int32_t
 }
 
 // ---- pass 3 with the batch's 128-sample tiles dealt to n_slices blocks per SNP chunk (see encode_bwd_fp4_kernel)
-#ifdef NADM_TEST_HOOKS
-static std::atomic<int> g_force_p3_slices{0};
-extern "C" void nadm_test_force_p3_slices(int32_t n) { g_force_p3_slices.store(n < 0 ? 0 : (n > NADM_MAX_P2_SLICES ? NADM_MAX_P2_SLICES : n)); }
-#endif
-
 extern "C" int32_t nadm_encode_slices(int32_t b, int64_t M, int32_t cp) {
     if (cp > 8 || b <= 0 || M <= 0) return 1;
     const int64_t chunks = (M + EB_CHUNK_SNPS - 1) / EB_CHUNK_SNPS;
     const int tiles = (b + DZI_TS - 1) / DZI_TS;
-    int s = 0;
-#ifdef NADM_TEST_HOOKS
-    s = g_force_p3_slices.load();
-#endif
+    int s = hook_p3_slices();                                       // 0 (always, in the shipping library): the rule below
     if (s == 0) {
         // Measured (profiles/r06_p3_slices.txt): a launch of ~120 chunk blocks that each walk 50 tiles (6400 rows x 62.5k SNPs, the SNP-sharded
         // rank of configs[3] on 8 GPUs) lasts as long as one block's chain, 77 us where the same genotypes as 977 blocks take 41; two slices

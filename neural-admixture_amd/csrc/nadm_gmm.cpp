@@ -24,7 +24,7 @@
 // The restarts are independent once their seeds are known: they run on threads of their own, and each splits its sums over the
 // samples into up to 64 fixed ranges swept by a few worker threads (n_parts, Fit).
 #include "../../include/nadm.h"
-#include "nadm_host.h"
+#include "nadm_err.h"
 #include <atomic>
 #include <cmath>
 #include <limits>

@@ -1,21 +1,10 @@
 // Host-side helpers shared by the C-ABI translation units.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <string.h>
-#include <math.h>
-#include "../../include/nadm.h"
+#include "nadm_err.h"
 
 namespace nadm {
 
-inline char* err_buf() {
-    static thread_local char buf[512] = {0};
-    return buf;
-}
-inline int fail(const char* msg) {
-    snprintf(err_buf(), 512, "%s", msg);
-    return 1;
-}
 inline int check_launch(const char* what) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -32,6 +21,16 @@ inline void adam_scalars(float lr, int step, float* step_size, float* inv_bc2) {
     *step_size = (float)((double)lr / bc1);
     *inv_bc2 = (float)(1.0 / sqrt(bc2));
 }
+
+// The test hooks (nadm_hooks.cpp): 0 = the library's own rule.  In libnadm.so they always return 0; in libnadm_testhooks.so they return
+// what nadm_test_force_slices / nadm_test_force_p3_slices / nadm_test_force_generic_mlp last set.
+int hook_p2_slices();
+int hook_p3_slices();
+int hook_generic_mlp();
+
+// the partial sums only (the first kernel of nadm_mlp_bwd_weights): used by the variants of pass 3 that cannot host them
+int mlp_bwd_weight_parts(const nadm_heads_t* hd, int32_t b, const float* Zn, const float* H, const float* dL, const float* dHpre,
+                         const float* dgp, float* small_part, void* stream);
 
 // The genotype passes as the plan's step runs them, with its matmul precision (NADM_PRECISION_*, nadm_plan_set_precision):
 // "highest" calls exactly the public entry point of that form (nadm_decode_bce_sliced / _images / _step, nadm_encode_fwd / _part /

@@ -40,47 +40,6 @@ using namespace nadm;
         }                                                                                        \
     } while (0)
 
-// ------------------------------------------------------------------------------------------------- flat layout
-static int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-static int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
-static int64_t lcm64(int64_t a, int64_t b) { return a / gcd64(a, b) * b; }
-
-extern "C" int nadm_flat_layout(const nadm_heads_t* hd, int64_t M, int32_t world, int32_t n_buckets, nadm_flat_layout_t* out) {
-    if (!hd || !out) return fail("nadm_flat_layout: null pointer");
-    if (M <= 0 || world < 1 || hd->n_heads < 1 || hd->n_heads > NADM_MAX_HEADS) return fail("nadm_flat_layout: M, world >= 1 and 1..32 heads");
-    if (n_buckets < 0 || n_buckets > NADM_MAX_BUCKETS) return fail("nadm_flat_layout: at most 8 buckets");
-    memset(out, 0, sizeof(*out));
-    const int64_t q = 4 * (int64_t)world;                               // a rank's slice is a multiple of 4 floats (16 bytes: the Adam kernel's vector accesses)
-    out->off_v = round_up(hd->n_small, lcm64(64, q));
-    // range boundaries of message B's buckets: multiples of U SNPs = a multiple of every pass's chunk (pass 1: 2048, pass 3: 512) whose
-    // V rows are a multiple of q floats, so that every bucket but the last is `world` slices without a gap
-    const int64_t U = lcm64(2048, q / gcd64(q, hd->CP));
-    const int64_t units = (M + U - 1) / U;
-    int64_t nb = n_buckets < 1 ? 1 : n_buckets;
-    if (nb > units) nb = units;
-    out->n_buckets = (int32_t)nb;
-    const int64_t b_end = round_up(out->off_v + M * hd->CP, q);
-    for (int64_t j = 0; j <= nb; ++j) {
-        const int64_t m = j == nb ? M : U * (j * units / nb);
-        out->bkt_m0[j] = m;
-        out->bkt_off[j] = j == 0 ? 0 : (j == nb ? b_end : out->off_v + m * hd->CP);
-    }
-    for (int64_t j = 0; j < nb; ++j) {
-        out->bkt_slice[j] = (out->bkt_off[j + 1] - out->bkt_off[j]) / world;
-        out->bkt_mom[j] = out->slice_b;
-        out->slice_b += out->bkt_slice[j];
-    }
-    out->msg_a_off = b_end;
-    int64_t off = out->msg_a_off;
-    for (int h = 0; h < hd->n_heads; ++h) {
-        out->off_p[h] = off;
-        off += M * hd->kp[h];
-    }
-    out->slice_a = round_up(off - out->msg_a_off, q) / world;
-    out->n_flat = out->msg_a_off + out->slice_a * world;
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------- RCCL transport
 namespace {
 
