@@ -554,6 +554,29 @@ int nadm_project_q(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b,
                    const float* P, int32_t k, int32_t kp, const float* Qin, float* Qout, int32_t q_stride,
                    float eps, float qmin, double* loglik, int32_t* nobs, float* scratch, void* stream);
 
+/* ---- the other half: refit P against a FIXED Q with a masked EM step -------------------------------------------------------
+ * With nadm_project_q this is the FRAPPE / ADMIXTURE block EM over the OBSERVED calls only.  One call = one step for the rows
+ * idx[0..b) (idx == NULL: rows 0..b; any order, a duplicate counts as often as it occurs), Q [b, k] (row s belongs to idx[s],
+ * row stride q_stride, a multiple of 4, >= kp, pad cols 0) and ONE head Pin [M, kp] (kp = nadm_pad_k(k), pad cols 0):
+ *     rr_ij = sum_k q_ik p_jk;   r = clip(rr, eps, 1 - eps);   u = clip(1 - rr, eps, 1 - eps)       (1 - r from the UNCLIPPED product)
+ *     B_jk  = sum over observed i of q_ik g_ij / r_ij          C_jk = sum over observed i of q_ik (2 - g_ij) / u_ij
+ *     num   = p_jk B_jk;   den = num + (1 - p_jk) C_jk
+ *     p'_jk = clip(num / den, pmin, 1 - pmin)  if den > 0,  else  p_jk with its bits unchanged (not clipped)
+ *     n_j   = number of observed i
+ * Pout [M, kp] may be Pin; its pad columns are written 0, rows >= M are never written; nobs_snp int32 [M] may be NULL.
+ * eps in [1e-9, 0.5), pmin in [0, 0.5) (both 1e-6 by default in the Python layer).  scratch: nadm_project_p_scratch_floats(b, M, kp)
+ * floats.  xp, Q, Pin, Pout, scratch 16-byte aligned; ld % 16 == 0, ld < 2^32.
+ * A missing call and a SNP >= M enter every sum as exactly +0.0f.  The batch's 64-sample tiles are cut into
+ * nadm_project_p_slices(b, M) slices of whole tiles (1 for b <= 64; more while M alone does not fill the chip; never more than
+ * 4096 samples in one slice): sums are fp32 within a slice in sample order, the slices' partials are added in float64 in slice
+ * order, num / den and the clip are float64.  The order depends on (b, M, kp) alone and there are no floating-point atomics:
+ * the same inputs give the same bits.  Every refusal is reported before anything is launched. */
+int32_t nadm_project_p_slices(int32_t b, int64_t M);
+int64_t nadm_project_p_scratch_floats(int32_t b, int64_t M, int32_t kp);
+int nadm_project_p(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                   const float* Q, int32_t q_stride, int32_t k, int32_t kp, const float* Pin, float* Pout,
+                   float eps, float pmin, int32_t* nobs_snp, float* scratch, void* stream);
+
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,
  * random_state=seed).fit(X).means_): the EM iterations of that call in float64 on the host (csrc/nadm_gmm.cpp restates the

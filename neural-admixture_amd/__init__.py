@@ -10,6 +10,7 @@ from .engine import Engine        # noqa: F401
 from .model import Q_P, NeuralAdmixture   # noqa: F401
 from .train import train          # noqa: F401
 from .project import project_q    # noqa: F401  (Q refined against a fixed P, no encoder needed)
+from .project import project_p, polish    # noqa: F401  (P refitted against a fixed Q; the two alternated)
 from . import pack2bit            # noqa: F401  (the reference's native module by its own names: pack2bit.cu:144-147)
 
-__all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q"]
+__all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish"]

@@ -62,6 +62,13 @@ def parse_train_args(argv):
     p.add_argument("--share_gpu", action="store_true",
                    help="functional check of a --num_gpus N run on a ONE-GPU box: every rank uses cuda:0 and gloo carries the "
                         "tensors (RCCL refuses two ranks per device)")
+    p.add_argument("--polish", type=int, default=0, metavar="N",
+                   help="after training, up to N rounds of block EM over the OBSERVED calls only (a Q step with P fixed, then a P step "
+                        "with the new Q), started from the trained P and the encoder's Q: the written .Q/.P are then a masked "
+                        "maximum-likelihood fit (training reads a missing call as genotype 0).  The .pt checkpoint stays as trained.  "
+                        "Single-GPU, unsupervised runs only.  0 (default): off")
+    p.add_argument("--polish_tol", type=float, default=1e-5,
+                   help="stop polishing once no entry of Q or P moves by this much in a round")
     _add_precision(p)
     return p.parse_args(argv)
 
@@ -120,7 +127,8 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
     Ps, Qs, model = train(args.epochs, args.batch_size, args.learning_rate, K, args.seed, data, device, num_gpus, args.hidden_size,
                           master, V, pops, args.min_k, args.max_k, args.n_components, parallelism=args.parallelism,
                           host_threads=args.threads, gmm=args.gmm, precision=args.precision,
-                          unlabelled=None if pops is None else (args.unlabelled,), supervised_loss_weight=args.supervised_loss_weight)
+                          unlabelled=None if pops is None else (args.unlabelled,), supervised_loss_weight=args.supervised_loss_weight,
+                          polish=args.polish, polish_tol=args.polish_tol)
     if master:
         save_model(model, args.name, args.save_dir)
         write_outputs(Qs, args.name, K, args.min_k, args.max_k, args.save_dir, Ps)
@@ -140,6 +148,12 @@ def main(argv=None):
     if mode == "train":
         args = parse_train_args(argv[1:])
         assert args.epochs > 0 and args.batch_size > 0 and args.learning_rate > 0 and args.hidden_size > 0 and args.n_components > 0
+        if args.polish < 0:
+            raise SystemExit("    --polish takes a number of rounds >= 0.")
+        if args.polish > 0 and args.num_gpus > 1:           # before any data is read
+            raise SystemExit("    --polish is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
+        if args.polish > 0 and args.pops_path:
+            raise SystemExit("    --polish ignores labels: it is not available with --pops_path (supervised runs).")
         pops = None
         if args.pops_path:                                  # src/utils.py:28-33: one population name per line
             with open(args.pops_path, "r") as fb:

@@ -554,6 +554,27 @@ class Engine:
         Qs = [q[:, :k].clone() for q, k in zip(Qs, L.ks)]
         return (Qs, lls, nobs) if with_loglik else Qs
 
+    def polish(self, rounds: int, tol: float = 1e-5):
+        """Block EM over the OBSERVED calls of the resident matrix, started from the engine's own P heads and the encoder's final Q
+        (project.polish: a Q step with P fixed, then a P step with the new Q, per head and round; stops after ``rounds`` or once
+        nothing moves by ``tol``).  Returns ``(Ps [M, k], Qs [N, k], ll_before, ll_after, rounds_run)``; the engine's parameters and
+        optimiser state are left as they are (the encoder was trained against its own P)."""
+        from . import project
+        if self.mode != "single" or self.world != 1:
+            raise NotImplementedError("Engine.polish is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
+                                      "P; polish with project.polish on one GPU from the written .P and .Q files instead")
+        if self._plan is None or self.xp is None:
+            raise RuntimeError("Engine.polish needs the HIP engine with its packed matrix resident (no CPU fallback)")
+        L = self.lay
+        N = int(self.xp.shape[0])
+        seq = torch.arange(N, dtype=torch.int32, device=self.device)
+        Qs = [[] for _ in L.ks]
+        for s in range(0, N, self.bmax):
+            bb = min(self.bmax, N - s)
+            for h, q in enumerate(self.infer_q(seq[s:s + bb], bb)):
+                Qs[h].append(q)
+        return project.polish(self.xp, L.M, [self.P(h) for h in range(len(L.ks))], [torch.cat(q, dim=0) for q in Qs], rounds, tol)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()

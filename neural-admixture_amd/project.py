@@ -1,8 +1,13 @@
-"""Projection: fit Q to a FIXED P by maximum likelihood over the OBSERVED calls only (what ADMIXTURE calls -P).
+"""Projection: fit Q to a FIXED P by maximum likelihood over the OBSERVED calls only (what ADMIXTURE calls -P), its counterpart for P
+against a fixed Q, and the two alternated (``polish``): the FRAPPE / ADMIXTURE block EM over observed calls.
 
 ``project_q`` needs no encoder: a packed genotype matrix in HBM and a host ``P [M, K]`` (a ``.P`` file) are enough.  Every
 iteration is one call of ``nadm_project_q`` (include/nadm.h: one masked EM step of the binomial admixture model, two launches,
 reproducible bit for bit); ``Engine.project_q`` runs the same loop on the engine's own P with the encoder's Q as the start.
+
+``project_p`` is the other half: allele frequencies for given ancestry fractions (a ``.Q`` file, say) and any genotype matrix, one
+``nadm_project_p`` call per iteration.  ``polish`` alternates the two from a trained model's answer; ``Engine.polish`` and
+``train(..., polish=N)`` run it on the resident matrix.
 """
 from __future__ import annotations
 
@@ -16,6 +21,8 @@ from ._lib import lib, check, ptr
 
 EPS = 1e-6           # clip of the reconstruction: the log-likelihood report's (report.py)
 QMIN = 1e-6          # floor of an ancestry fraction before the renormalisation
+PMIN = 1e-6          # clip of a refitted allele frequency: [PMIN, 1 - PMIN]
+POLISH_ROWS = 1024   # rows per Q step of polish(): bounds nadm_project_scratch_floats whatever N is
 
 
 def _stream():
@@ -114,6 +121,104 @@ def project_q(xp: torch.Tensor, M: int, P, q0=None, iters: int = 20, tol: float 
     Qs, lls, nobs, _ = refine_heads(xp, M, idx, b, [Pp], [K], [q], iters, tol, eps, qmin, with_loglik)
     Q = Qs[0][:, :K].clone()
     return (Q, lls[0], nobs[0]) if with_loglik else Q
+
+
+def p_step(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor], b: int, Qp: torch.Tensor, k: int, pin: torch.Tensor,
+           pout: torch.Tensor, scratch: torch.Tensor, eps: float = EPS, pmin: float = PMIN, nobs_snp: Optional[torch.Tensor] = None) -> None:
+    """One ``nadm_project_p`` call on the current stream: ``Qp [b, >= kp]`` (row s belongs to ``idx[s]``), ``pin`` / ``pout [M, kp]``
+    (may be the same tensor), ``nobs_snp`` int32 [M] or None."""
+    kp = pin.shape[1]
+    check(lib.nadm_project_p(ptr(xp), xp.shape[1], ptr(idx), b, M, ptr(Qp), Qp.stride(0), k, kp, ptr(pin), ptr(pout), eps, pmin,
+                             ptr(nobs_snp), ptr(scratch), _stream()), "project_p")
+
+
+def _p_scratch(b: int, M: int, kps: Sequence[int], dev) -> torch.Tensor:
+    return torch.empty(max(max(int(lib.nadm_project_p_scratch_floats(b, M, kp)) for kp in kps), 4), dtype=torch.float32, device=dev)
+
+
+def _check_packed(xp: torch.Tensor, idx: Optional[torch.Tensor], b: int) -> None:
+    if xp.device.type != "cuda":
+        raise RuntimeError("the packed matrix must be on a ROCm GPU (no CPU fallback)")
+    if xp.dtype != torch.uint8 or xp.dim() != 2 or not xp.is_contiguous():
+        raise RuntimeError("packed genotypes must be a contiguous uint8 [rows, ld] matrix")
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() < b):
+        raise RuntimeError("idx must be an int32 tensor of at least b rows")
+
+
+def project_p(xp: torch.Tensor, M: int, Q, p0=None, iters: int = 20, tol: float = 1e-5, idx: Optional[torch.Tensor] = None,
+              b: Optional[int] = None, eps: float = EPS, pmin: float = PMIN) -> torch.Tensor:
+    """Allele frequencies ``P [M, K]`` (float32, on xp's device) of the packed device matrix ``xp [rows, ld]`` for the FIXED ancestry
+    fractions ``Q [b, K]`` of its rows ``idx[0..b)`` (default: every row): ``iters`` masked EM steps from ``p0 [M, K]``, stopping
+    early once no entry moves by ``tol``.  ``p0 = None`` starts every entry at 0.5; the first step then yields the ancestry-weighted
+    allele frequencies.  The SNPs need not be ones a model was trained on."""
+    if b is None:
+        b = int(idx.numel()) if idx is not None else int(xp.shape[0])
+    _check_packed(xp, idx, b)
+    K = int(np.shape(Q)[1])
+    kp = int(lib.nadm_pad_k(K))
+    if kp <= 0:
+        raise RuntimeError("K must be in 1..64")
+    Qp = pad_Q(Q, b, K, kp, xp.device)
+    cur = pad_P(np.full((M, K), 0.5, dtype=np.float32) if p0 is None else p0, xp.device)
+    if tuple(cur.shape) != (M, kp):
+        raise RuntimeError(f"p0 must be [{M}, {K}]")
+    nxt = torch.empty_like(cur)
+    scratch = _p_scratch(b, M, [kp], xp.device)
+    for _ in range(int(iters)):
+        p_step(xp, M, idx, b, Qp, K, cur, nxt, scratch, eps, pmin)
+        delta = float((nxt - cur).abs().max())
+        cur, nxt = nxt, cur
+        if delta < tol:
+            break
+    return cur[:, :K].clone()
+
+
+def _summed_loglik(xp: torch.Tensor, M: int, N: int, Pps, ks, Qps, rows: int, eps: float, qmin: float) -> float:
+    """Log-likelihood of the observed calls summed over the rows 0..N and the heads, in float64: the ``ll`` of a Q step that moves
+    nothing (``refine_heads`` with ``iters = 0``), in row batches."""
+    total = 0.0
+    for s in range(0, N, rows):
+        bb = min(rows, N - s)
+        _, lls, _, _ = refine_heads(xp[s:s + bb], M, None, bb, Pps, ks, [q[s:s + bb] for q in Qps], 0, 0.0, eps, qmin, with_loglik=True)
+        total += float(sum(ll.sum() for ll in lls))
+    return total
+
+
+def polish(xp: torch.Tensor, M: int, Ps: Sequence, Qs: Sequence, rounds: int, tol: float = 1e-5, eps: float = EPS, qmin: float = QMIN,
+           pmin: float = PMIN):
+    """Block EM over the observed calls from a given answer: per head ``h``, ``Ps[h] [M, k_h]`` and ``Qs[h] [N, k_h]`` (host or device;
+    N = the rows of ``xp``) are alternately refitted -- one round is a Q step over all rows with P fixed (in batches of POLISH_ROWS
+    rows), then a P step over all rows with the new Q -- for ``rounds`` rounds, or until max |dQ| and max |dP| of a round are both
+    below ``tol`` over all heads.  Returns ``(Ps, Qs, ll_before, ll_after, rounds_run)``: float32 device matrices ``[M, k_h]`` /
+    ``[N, k_h]`` and the log-likelihood of the observed calls summed over samples and heads (float64) at the start and at the end."""
+    N = int(xp.shape[0])
+    _check_packed(xp, None, N)
+    dev = xp.device
+    ks = [int(np.shape(P)[1]) for P in Ps]
+    Pc = [pad_P(P, dev) for P in Ps]
+    Qc = [pad_Q(Q, N, k, Pp.shape[1], dev) for Q, k, Pp in zip(Qs, ks, Pc)]
+    if any(Pp.shape[0] != M for Pp in Pc):
+        raise RuntimeError(f"every P must have {M} rows, one per SNP")
+    rows = min(POLISH_ROWS, N)
+    q_scratch = torch.empty(max(max(int(lib.nadm_project_scratch_floats(rows, M, Pp.shape[1])) for Pp in Pc), 4), dtype=torch.float32, device=dev)
+    p_scratch = _p_scratch(N, M, [Pp.shape[1] for Pp in Pc], dev)
+    ll_before = _summed_loglik(xp, M, N, Pc, ks, Qc, rows, eps, qmin)
+    done = 0
+    for _ in range(int(rounds)):
+        delta = torch.zeros((), dtype=torch.float32, device=dev)
+        for h, k in enumerate(ks):
+            qn, pn = torch.empty_like(Qc[h]), torch.empty_like(Pc[h])
+            for s in range(0, N, rows):
+                bb = min(rows, N - s)
+                em_step(xp[s:s + bb], M, None, bb, Pc[h], k, Qc[h][s:s + bb], qn[s:s + bb], q_scratch, eps, qmin)
+            p_step(xp, M, None, N, qn, k, Pc[h], pn, p_scratch, eps, pmin)
+            delta = torch.maximum(delta, torch.maximum((qn - Qc[h]).abs().max(), (pn - Pc[h]).abs().max()))
+            Qc[h], Pc[h] = qn, pn
+        done += 1
+        if float(delta) < tol:
+            break
+    ll_after = _summed_loglik(xp, M, N, Pc, ks, Qc, rows, eps, qmin) if done else ll_before
+    return [P[:, :k].clone() for P, k in zip(Pc, ks)], [Q[:, :k].clone() for Q, k in zip(Qc, ks)], ll_before, ll_after, done
 
 
 def find_P_files(save_dir: str, name: str, ks: Sequence[int]) -> List[str]:

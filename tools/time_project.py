@@ -1,13 +1,14 @@
-"""Time one projection step (nadm_project_q, include/nadm.h) next to the parent's pass 2 at the same shape.
-    python tools/time_project.py [--b 800] [--M 500000] [--K 8] [--rounds 30] [--out profiles/project_q.txt]
+"""Time one projection step (nadm_project_q, include/nadm.h) and its counterpart for P (nadm_project_p) next to pass 2 at the same shape.
+    python tools/time_project.py [--b 800] [--M 500000] [--K 8] [--rounds 30] [--out profiles/project_p.txt]
 
-Three launch groups on the same resident matrix (admixture-model genotypes from nadm_synth_packed, 2 % missing, the batch = b random
+Four launch groups on the same resident matrix (admixture-model genotypes from nadm_synth_packed, 2 % missing, the batch = b random
 rows of 4 b resident ones), the same P and Q:
     project        nadm_project_q, loglik == NULL (an iteration of the refinement: accumulate + fold)
     project+ll     nadm_project_q with loglik (the logarithms; the first and the last pass of a refinement)
+    project_p      nadm_project_p (the P step of a polish round: accumulate + fold)
     pass2          nadm_decode_bce, with_loss = 1, no Adam: the same two products Q.P^T and dR.P plus dP, the yardstick
-Each is warmed up, then timed with device events over `rounds` rounds in which the three alternate (what shares the box shifts all
-three alike); a timed window is 10 back-to-back calls.  Reported: the median per call and the quartiles, and the ratios to pass 2."""
+Each is warmed up, then timed with device events over `rounds` rounds in which the four alternate (what shares the box shifts all
+four alike); a timed window is 10 back-to-back calls.  Reported: the median per call and the quartiles, and the ratios to pass 2."""
 import argparse
 import ctypes as C
 import sys
@@ -25,7 +26,7 @@ ap.add_argument("--M", type=int, default=500_000)
 ap.add_argument("--K", type=int, default=8)
 ap.add_argument("--rounds", type=int, default=30)
 ap.add_argument("--calls", type=int, default=10)
-ap.add_argument("--out", default="profiles/project_q.txt")
+ap.add_argument("--out", default="profiles/project_p.txt")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "time_project.py measures on the GPU; there is no fallback"
 dev = torch.device("cuda:0")
@@ -46,6 +47,9 @@ Qo = torch.empty_like(Q)
 ll = torch.empty(b, dtype=torch.float64, device=dev)
 nobs = torch.empty(b, dtype=torch.int32, device=dev)
 scratch = torch.empty(int(lib.nadm_project_scratch_floats(b, M, kp)), dtype=torch.float32, device=dev)
+Po = torch.empty_like(P)
+nsnp = torch.empty(M, dtype=torch.int32, device=dev)
+p_scratch = torch.empty(int(lib.nadm_project_p_scratch_floats(b, M, kp)), dtype=torch.float32, device=dev)
 chunks = int(lib.nadm_decode_chunks(M, kp))
 dP, dq, loss = torch.empty_like(P), torch.empty(chunks * b * kp, dtype=torch.float32, device=dev), torch.empty(chunks, dtype=torch.float32, device=dev)
 
@@ -55,11 +59,16 @@ def project(with_ll):
                              ptr(nobs), ptr(scratch), st), "project_q")
 
 
+def project_p():
+    check(lib.nadm_project_p(ptr(xp), ld, ptr(idx), b, M, ptr(Q), kp, K, kp, ptr(P), ptr(Po), 1e-6, 1e-6, ptr(nsnp), ptr(p_scratch), st),
+          "project_p")
+
+
 def pass2():
     check(lib.nadm_decode_bce(ptr(xp), ld, ptr(idx), b, M, ptr(P), kp, ptr(Q), kp, ptr(dP), ptr(dq), ptr(loss), 1, st), "decode_bce")
 
 
-groups = {"project": lambda: project(False), "project+ll": lambda: project(True), "pass2": pass2}
+groups = {"project": lambda: project(False), "project+ll": lambda: project(True), "project_p": project_p, "pass2": pass2}
 for f in groups.values():                                   # warm-up: code objects, caches, clocks
     for _ in range(5):
         f()
@@ -80,10 +89,12 @@ lines = [f"tools/time_project.py: b = {b}, M = {M}, K = {K} (kp = {kp}), {rows} 
 for n in groups:
     lines.append(f"  {n:11s} {q[n][1]:8.4f}  [{q[n][0]:.4f}, {q[n][2]:.4f}]")
 lines.append(f"  project / pass2 = {q['project'][1] / q['pass2'][1]:.3f}   project+ll / pass2 = {q['project+ll'][1] / q['pass2'][1]:.3f}   "
-             f"project+ll / project = {q['project+ll'][1] / q['project'][1]:.3f}")
+             f"project+ll / project = {q['project+ll'][1] / q['project'][1]:.3f}   project_p / pass2 = {q['project_p'][1] / q['pass2'][1]:.3f}   "
+             f"project_p / project = {q['project_p'][1] / q['project'][1]:.3f}")
 pairs = b * M
 lines.append(f"  (sample, SNP) pairs per call {pairs:.3e}: project {pairs / q['project'][1] / 1e6:.1f} G pairs/s, packed bytes read {b * ld / 1e6:.1f} MB, "
-             f"partials written + read {2 * 4 * scratch.numel() / 1e6:.1f} MB")
+             f"partials written + read {2 * 4 * scratch.numel() / 1e6:.1f} MB; project_p {pairs / q['project_p'][1] / 1e6:.1f} G pairs/s, "
+             f"{int(lib.nadm_project_p_slices(b, M))} sample slice(s), partials at most {2 * 4 * p_scratch.numel() / 1e6:.1f} MB")
 text = "\n".join(lines) + "\n"
 print(text, end="")
 with open(a.out, "w") as fb:
