@@ -577,6 +577,37 @@ int nadm_project_p(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b,
                    const float* Q, int32_t q_stride, int32_t k, int32_t kp, const float* Pin, float* Pout,
                    float eps, float pmin, int32_t* nobs_snp, float* scratch, void* stream);
 
+/* ---- admixture-aware kinship (REAP, Thornton et al. 2012) of one block of sample pairs ---------------------------------------
+ * Pairwise kinship from individual-specific allele frequencies: the check of the model's assumption that the samples are
+ * unrelated.  One call = the rows idxA[0..ba) against the rows idxB[0..bb) (idx == NULL: rows 0..b; any order, a duplicate row
+ * is allowed, the two lists may be the same), QA [ba, k] / QB [bb, k] (row s belongs to idx[s], row stride q_stride, a multiple
+ * of 4, >= kp, pad cols 0; may be the same pointer) and ONE head P [M, kp] (kp = nadm_pad_k(k), pad cols 0).  Codes g in
+ * {0, 1, 2} are observed, 3 is missing:
+ *     pi_ij  = sum_k q_ik p_jk                                      (fp32, fused multiply-adds, k in order)
+ *     m_ij   = 1 if the call is observed, j < M and pimin <= pi_ij <= 1 - pimin (1 - pimin rounded to fp32), else 0
+ *     d_ij   = m_ij (g_ij - 2 pi_ij)        s_ij = m_ij sqrt(max(pi_ij (1 - pi_ij), 0))
+ *     num_ab = sum_j d_aj d_bj      den_ab = sum_j s_aj s_bj      n_ab = sum_j m_aj m_bj
+ * The kinship coefficient is phi_ab = num_ab / (4 den_ab) (the caller divides; den_ab = 0 has none), the inbreeding coefficient
+ * of a sample f_a = 2 phi_aa - 1.  num, den double [ba, bb], nobs int32 [ba, bb] (may be NULL), row-major.  pimin in [0, 0.5);
+ * 0 lets every observed call with 0 <= pi <= 1 count -- the test on pi stays: a Q row that sums to 1 + ulp against a P of 1.0
+ * gives a pi just above 1 in fp32, and that call is dropped (its s would be 0 anyway).  ba, bb in 1..NADM_KINSHIP_MAX_ROWS.  scratch: nadm_kinship_scratch_floats(ba, bb, M) floats
+ * (grows with ba, bb and M).  xp, P, QA, QB, scratch 16-byte aligned; ld % 16 == 0, ld < 2^32.
+ * A missing call, a SNP >= M and a masked pi enter all three sums as exactly +0.0f (the result does not depend on P where both
+ * calls are missing, nor on the pad bits of a row's last byte).  d and s are carried as two round-to-nearest bf16 pieces each
+ * (value to 2^-17 relative) and multiplied on the matrix pipe as hi.hi + hi.lo + lo.hi with fp32 accumulation (the dropped
+ * lo.lo term is below 2^-16 of |d_a||d_b|); m is exact in one piece.  The 256-SNP chunks are cut into
+ * nadm_kinship_ranges(ba, bb, M) contiguous ranges (more than one while the 64 x 64 tiles of the block alone do not fill the
+ * chip); one fp32 accumulator never covers more than 2^18 SNPs, so n -- a sum of ones below 2^24 -- is exact.  The ranges'
+ * partials are added in float64 in range order.  The order depends on (ba, bb, M, kp) alone and there are no floating-point
+ * atomics: the same inputs give the same bits.  kp <= 16 keeps a sample's Q row in registers, wider heads re-read it.
+ * Every refusal is reported before anything is launched. */
+#define NADM_KINSHIP_MAX_ROWS 4096
+int32_t nadm_kinship_ranges(int32_t ba, int32_t bb, int64_t M);
+int64_t nadm_kinship_scratch_floats(int32_t ba, int32_t bb, int64_t M);
+int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
+                 const float* P, int32_t k, int32_t kp, const float* QA, const float* QB, int32_t q_stride, float pimin,
+                 double* num, double* den, int32_t* nobs, float* scratch, void* stream);
+
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,
  * random_state=seed).fit(X).means_): the EM iterations of that call in float64 on the host (csrc/nadm_gmm.cpp restates the

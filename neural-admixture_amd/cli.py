@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -93,6 +93,82 @@ def parse_infer_args(argv):
     return p.parse_args(argv)
 
 
+def parse_kinship_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture kinship",
+                                description="Admixture-aware kinship (REAP) of the samples from a run's .P and .Q files")
+    p.add_argument("--data_path", required=True, type=str)
+    p.add_argument("--save_dir", required=True, type=str)
+    p.add_argument("--name", required=True, type=str)
+    p.add_argument("--k", required=True, type=int)
+    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
+    p.add_argument("--min_phi", type=float, default=2.0 ** -4.5,
+                   help="list the pairs with a kinship coefficient of at least this (default 0.0442, the lower edge of third-degree relatives)")
+    p.add_argument("--pimin", type=float, default=0.0,
+                   help="drop a call whose individual-specific allele frequency is outside [pimin, 1 - pimin] (default 0: every observed call counts)")
+    p.add_argument("--threads", type=int, default=1)
+    return p.parse_args(argv)
+
+
+def _kinship_main(argv, t0):
+    """``kinship`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.kin (``i j phi n`` per related pair, 0-based
+    sample indices, by i then j) and {out_name}.{k}.inbreed (one inbreeding coefficient per sample)."""
+    from . import relate
+    from .project import find_P_files, read_P_files
+    from .io import savetxt
+    args = parse_kinship_args(argv)
+    if args.k < 1 or args.k > 64:
+        raise SystemExit("    --k must be in 1..64.")
+    if not 0.0 <= args.pimin < 0.5:
+        raise SystemExit("    --pimin must be in [0, 0.5).")
+    if not args.min_phi == args.min_phi:
+        raise SystemExit("    --min_phi must be a number.")
+    name = os.path.basename(args.data_path)
+    if ".bed" not in name and ".vcf" not in name:
+        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
+    P_path = find_P_files(args.save_dir, args.name, [args.k], what="kinship")[0]   # before anything is read
+    Q_path = relate.find_Q_files(args.save_dir, args.name, [args.k])[0]
+    n_known = m_known = None
+    if ".bed" in name:                                      # the .fam file and the size of the .bed give N and M without reading a genotype
+        from pathlib import Path
+        fam, bed = Path(args.data_path).with_suffix(".fam"), Path(args.data_path).with_suffix(".bed")
+        for f in (fam, bed):
+            if not f.is_file():
+                raise SystemExit(f"    {f} not found.")
+        with open(fam) as fb:
+            n_known = sum(1 for _ in fb)
+        nb = (n_known + 3) // 4
+        if n_known < 1 or (bed.stat().st_size - 3) < nb or (bed.stat().st_size - 3) % nb:
+            raise SystemExit(f"    {bed} does not hold whole SNPs of the {n_known} samples of {fam}.")
+        m_known = (bed.stat().st_size - 3) // nb
+    # both files are read and checked before the genotypes: the widths always, the row counts where the input tells N and M up front
+    # (.bed); a VCF's are known only once it is parsed, and are checked then
+    Q = relate.read_matrix_file(Q_path, args.k, n_known)
+    P = read_P_files([P_path], [args.k], m_known)[0] if m_known is not None else relate.read_matrix_file(P_path, args.k, None)
+    if not torch.cuda.is_available():
+        raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
+    torch.set_num_threads(max(1, args.threads))
+    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True)
+    for path, a, rows in ((Q_path, Q, data.N), (P_path, P, data.M)):
+        if a.shape[0] != rows:
+            raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the data needs {rows} x {args.k}.")
+    i, j, phi, n, inb = relate.kinship_pairs(data.packed, data.M, P, Q, args.min_phi, pimin=args.pimin)
+    phi_h = phi.cpu().numpy()
+    out = args.out_name or args.name
+    os.makedirs(args.save_dir, exist_ok=True)
+    relate.write_pairs(os.path.join(args.save_dir, f"{out}.{args.k}.kin"), i.cpu().numpy(), j.cpu().numpy(), phi_h, n.cpu().numpy())
+    savetxt(os.path.join(args.save_dir, f"{out}.{args.k}.inbreed"), inb.cpu().numpy().reshape(-1, 1))
+    log.info(f"    {len(phi_h)} pairs with a kinship coefficient >= {args.min_phi:.4f} among {data.N} samples:")
+    for label, edge, count in relate.band_counts(phi_h):
+        log.info(f"      {label} (>= {edge:.4f}): {count}")
+    close = int((phi_h >= relate.BANDS[2][0]).sum())
+    if close:
+        log.info(f"    Warning: {close} pairs are second-degree relatives or closer; related samples bias the fit "
+                 "(the model assumes unrelated samples): consider removing one sample of each pair and training again.")
+    log.info("    Kinship and inbreeding coefficients saved.")
+    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
+    return 0
+
+
 def _read(path, device=None, keep_on_device=False):
     from .io import read_bed_packed, read_vcf_packed
     name = os.path.basename(path)
@@ -141,8 +217,10 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer"), 'Please provide either the argument "train" or "infer" to choose running mode.'
+    assert argv and argv[0] in ("train", "infer", "kinship"), 'Please provide either the argument "train" or "infer" to choose running mode.'
     mode, t0 = argv[0], time.time()
+    if mode == "kinship":                                   # (its argument and file checks come before the GPU check)
+        return _kinship_main(argv[1:], t0)
     if not torch.cuda.is_available():
         raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
     if mode == "train":

@@ -11,6 +11,7 @@ hipcc $FLAGS -c nadm_gmm_dev.hip -o nadm_gmm_dev.o "$@"         # the decoder-in
 hipcc $FLAGS -c nadm_calib.hip -o nadm_calib.o "$@"             # measurement helper: the box fingerprint of bench.py (not on the training path)
 hipcc $FLAGS -c nadm_project.hip -o nadm_project.o "$@"         # projection: Q refined against a fixed P (nadm_project_q; not on the training path)
 hipcc $FLAGS -c nadm_project_p.hip -o nadm_project_p.o "$@"     # the other half: P refitted against a fixed Q (nadm_project_p; not on the training path)
+hipcc $FLAGS -c nadm_kinship.hip -o nadm_kinship.o "$@"         # admixture-aware kinship from Q and P on the matrix pipe (nadm_kinship; not on the training path)
 # host-only units, compiled as plain C++ (no device pass)
 hipcc $HOST -c nadm_gmm.cpp -o nadm_gmm.o "$@"                  # decoder-init mixture fit on the host
 hipcc $HOST -c nadm_host_io.cpp -o nadm_host_io.o "$@"          # host packer, .bed converter, VCF parser, savetxt
@@ -20,7 +21,7 @@ hipcc $HOST -c nadm_layout.cpp -o nadm_layout.o "$@"            # head table + f
 # linked into both.  The tests that need a hook re-run themselves in a child process against the TEST build (tests/conftest.py: in_hook_build).
 hipcc $HOST -c nadm_hooks.cpp -o nadm_hooks.o "$@"
 hipcc $HOST -DNADM_TEST_HOOKS -c nadm_hooks.cpp -o nadm_hooks_th.o "$@"
-OBJS="nadm_genotype_passes.o nadm_small_kernels.o nadm_step.o nadm_gmm.o nadm_gmm_dev.o nadm_calib.o nadm_project.o nadm_project_p.o nadm_host_io.o nadm_layout.o"
+OBJS="nadm_genotype_passes.o nadm_small_kernels.o nadm_step.o nadm_gmm.o nadm_gmm_dev.o nadm_calib.o nadm_project.o nadm_project_p.o nadm_kinship.o nadm_host_io.o nadm_layout.o"
 hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-soname,libnadm.so -o libnadm.so $OBJS nadm_hooks.o -lpthread -ldl
 echo "built $(pwd)/libnadm.so"
 hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-soname,libnadm.so -o libnadm_testhooks.so $OBJS nadm_hooks_th.o -lpthread -ldl

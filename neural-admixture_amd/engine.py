@@ -575,6 +575,25 @@ class Engine:
                 Qs[h].append(q)
         return project.polish(self.xp, L.M, [self.P(h) for h in range(len(L.ks))], [torch.cat(q, dim=0) for q in Qs], rounds, tol)
 
+    def kinship(self, head: int = 0, min_phi: Optional[float] = None, pimin: float = 0.0):
+        """Admixture-aware kinship (REAP) of the resident matrix's samples from head ``head``'s P and the encoder's final Q
+        (relate.kinship_pairs; include/nadm.h, nadm_kinship): ``(i, j, phi, n, inbreeding)``, the pairs i < j with phi >= ``min_phi``
+        (default: the lower edge of third-degree relatives) and every sample's inbreeding coefficient.  A check of the model's
+        assumption that the samples are unrelated; the engine's parameters and optimiser state are left as they are."""
+        from . import relate
+        if self.mode != "single" or self.world != 1:
+            raise NotImplementedError("Engine.kinship is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
+                                      "P; use relate.kinship_pairs on one GPU from the written .P and .Q files instead")
+        if self._plan is None or self.xp is None:
+            raise RuntimeError("Engine.kinship needs the HIP engine with its packed matrix resident (no CPU fallback)")
+        L = self.lay
+        if not 0 <= head < len(L.ks):
+            raise RuntimeError(f"Engine.kinship: head must be in 0..{len(L.ks) - 1}")
+        N = int(self.xp.shape[0])
+        seq = torch.arange(N, dtype=torch.int32, device=self.device)
+        Q = torch.cat([self.infer_q(seq[s:s + self.bmax], min(self.bmax, N - s))[head] for s in range(0, N, self.bmax)], dim=0)
+        return relate.kinship_pairs(self.xp, L.M, self.P(head), Q, relate.MIN_PHI if min_phi is None else min_phi, pimin=pimin)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()

@@ -221,13 +221,13 @@ def polish(xp: torch.Tensor, M: int, Ps: Sequence, Qs: Sequence, rounds: int, to
     return [P[:, :k].clone() for P, k in zip(Pc, ks)], [Q[:, :k].clone() for Q, k in zip(Qc, ks)], ll_before, ll_after, done
 
 
-def find_P_files(save_dir: str, name: str, ks: Sequence[int]) -> List[str]:
-    """The paths ``{save_dir}/{name}.{k}.P`` for every k; a missing file ends the run, naming it."""
+def find_P_files(save_dir: str, name: str, ks: Sequence[int], what: str = "--refine") -> List[str]:
+    """The paths ``{save_dir}/{name}.{k}.P`` for every k; a missing file ends the run, naming it (``what``: who asks)."""
     import os
     paths = [os.path.join(save_dir, f"{name}.{k}.P") for k in ks]
     for p in paths:
         if not os.path.isfile(p):
-            raise SystemExit(f"    --refine needs the allele frequencies the training run wrote: {p} not found.")
+            raise SystemExit(f"    {what} needs the allele frequencies the training run wrote: {p} not found.")
     return paths
 
 

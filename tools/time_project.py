@@ -8,7 +8,12 @@ rows of 4 b resident ones), the same P and Q:
     project_p      nadm_project_p (the P step of a polish round: accumulate + fold)
     pass2          nadm_decode_bce, with_loss = 1, no Adam: the same two products Q.P^T and dR.P plus dP, the yardstick
 Each is warmed up, then timed with device events over `rounds` rounds in which the four alternate (what shares the box shifts all
-four alike); a timed window is 10 back-to-back calls.  Reported: the median per call and the quartiles, and the ratios to pass 2."""
+four alike); a timed window is 10 back-to-back calls.  Reported: the median per call and the quartiles, and the ratios to pass 2.
+
+    python tools/time_project.py --kinship [--b 1024] [--M 500000] [--K 8] [--rounds 10] [--out profiles/kinship.txt]
+The kinship leg (nadm_kinship, relate.py): one b x b block of sample pairs at M SNPs next to a plain torch formulation of the same block
+on the same GPU (per slab of 16384 SNPs: unpack, pi = Q.P^T, the mask, d and s in fp32, then D.D^T, S.S^T and m.m^T as fp32 matmuls --
+in this tool only), and the whole pair list of the configs[1] shape (2504 x 600k) through relate.kinship_pairs."""
 import argparse
 import ctypes as C
 import sys
@@ -21,13 +26,18 @@ from neural_admixture_amd._lib import lib, check, ptr  # noqa: E402
 from neural_admixture_amd.layout import ModelLayout  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--b", type=int, default=800)
+ap.add_argument("--b", type=int, default=None, help="rows of the batch / of a block side (default 800; 1024 with --kinship)")
 ap.add_argument("--M", type=int, default=500_000)
 ap.add_argument("--K", type=int, default=8)
 ap.add_argument("--rounds", type=int, default=30)
 ap.add_argument("--calls", type=int, default=10)
-ap.add_argument("--out", default="profiles/project_p.txt")
+ap.add_argument("--out", default=None)
+ap.add_argument("--kinship", action="store_true", help="the kinship leg instead of the projection groups")
 a = ap.parse_args()
+if a.out is None:
+    a.out = "profiles/kinship.txt" if a.kinship else "profiles/project_p.txt"
+if a.b is None:
+    a.b = 1024 if a.kinship else 800
 assert torch.cuda.is_available(), "time_project.py measures on the GPU; there is no fallback"
 dev = torch.device("cuda:0")
 b, M, K = a.b, a.M, a.K
@@ -43,6 +53,88 @@ P = torch.zeros((M, kp), dtype=torch.float32, device=dev)
 P[:, :K] = Fq.T
 Q = torch.zeros((b, kp), dtype=torch.float32, device=dev)
 Q[:, :K] = torch.from_numpy(rng.dirichlet(np.ones(K), size=b).astype(np.float32)).to(dev)
+
+
+def kinship_leg():
+    from neural_admixture_amd import relate
+    num = torch.empty((b, b), dtype=torch.float64, device=dev)
+    den, nn = torch.empty_like(num), torch.empty((b, b), dtype=torch.int32, device=dev)
+    k_scratch = relate.kinship_scratch(b, b, M, dev)
+    idb = torch.from_numpy(rng.permutation(rows)[:b].astype(np.int32)).to(dev)
+
+    def hip():
+        check(lib.nadm_kinship(ptr(xp), ld, ptr(idx), b, ptr(idb), b, M, ptr(P), K, kp, ptr(Q), ptr(Q), kp, 0.0, ptr(num), ptr(den), ptr(nn),
+                               ptr(k_scratch), st), "kinship")
+
+    slab = 16384
+    shifts = torch.tensor([0, 2, 4, 6], dtype=torch.uint8, device=dev)
+
+    def side(rows_idx, j0, j1):
+        by = xp[rows_idx.long(), j0 // 4:(j1 + 3) // 4]
+        code = ((by[:, :, None] >> shifts) & 3).reshape(by.shape[0], -1)[:, :j1 - j0]
+        pi = Q[:, :K] @ P[j0:j1, :K].T
+        m = (code != 3).to(torch.float32)
+        return m * (code.to(torch.float32) - 2.0 * pi), m * torch.sqrt(torch.clamp(pi * (1.0 - pi), min=0.0)), m
+
+    def plain():
+        n_ = torch.zeros((b, b), dtype=torch.float32, device=dev)
+        d_, s_ = torch.zeros_like(n_), torch.zeros_like(n_)
+        for j0 in range(0, M, slab):
+            j1 = min(M, j0 + slab)
+            da, sa, ma = side(idx, j0, j1)
+            db, sb, mb = side(idb, j0, j1)
+            d_ += da @ db.T
+            s_ += sa @ sb.T
+            n_ += ma @ mb.T
+        return d_, s_, n_
+
+    for _ in range(2):
+        hip()
+        want = plain()
+    torch.cuda.synchronize()
+    agree = float(((num - want[0].double()).abs() / want[1].double()).max())
+    t = {"nadm_kinship": [], "torch fp32": []}
+    for _ in range(a.rounds):
+        for name, f in (("nadm_kinship", hip), ("torch fp32", plain)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            t[name].append(e0.elapsed_time(e1))
+    q = {n: np.percentile(v, [25, 50, 75]) for n, v in t.items()}
+    macs = float(b) * b * M
+    lines = [f"tools/time_project.py --kinship: one {b} x {b} block, M = {M}, K = {K} (kp = {kp}), {rows} resident rows; {torch.cuda.get_device_name(0)}",
+             f"device events, {a.rounds} rounds, the two alternating; ms per block: median [quartiles]"]
+    for n in t:
+        lines.append(f"  {n:13s} {q[n][1]:9.3f}  [{q[n][0]:.3f}, {q[n][2]:.3f}]   {macs / q[n][1] / 1e9:.1f} T pair-SNPs/s")
+    lines.append(f"  nadm_kinship / torch fp32 = {q['nadm_kinship'][1] / q['torch fp32'][1]:.3f}; {int(lib.nadm_kinship_ranges(b, b, M))} ranges; "
+                 f"max |num - num_torch| / den = {agree:.2e}")
+    # the whole pair list of the configs[1] shape
+    N1, M1 = 2504, 600_000
+    ld1 = ModelLayout.row_stride(M1)
+    F1 = torch.from_numpy(np.clip(0.5 * rng.beta(0.5, 0.5, size=(K, M1)), 0.005, 0.5).astype(np.float32)).to(dev)
+    Q1 = torch.from_numpy(rng.dirichlet(0.2 * np.ones(K), size=N1).astype(np.float32)).to(dev)
+    x1 = torch.zeros((N1, ld1), dtype=torch.uint8, device=dev)
+    check(lib.nadm_synth_packed(ptr(x1), N1, 0, M1, ld1, ptr(Q1), ptr(F1), K, 0.02, 7, st), "synth_packed")
+    relate.kinship_pairs(x1, M1, F1.T, Q1)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    i_, j_, p_, n_, f_ = relate.kinship_pairs(x1, M1, F1.T, Q1)
+    e1.record()
+    e1.synchronize()
+    lines.append(f"  relate.kinship_pairs at {N1} x {M1}, K = {K} (6 blocks of up to 1024 x 1024): {e0.elapsed_time(e1):.1f} ms, "
+                 f"{i_.numel()} pairs at or above {relate.MIN_PHI:.4f} among unrelated synthetic samples, max |f| = {float(f_.abs().max()):.4f}")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    with open(a.out, "w") as fb:
+        fb.write(text)
+
+
+if a.kinship:
+    kinship_leg()
+    sys.exit(0)
 Qo = torch.empty_like(Q)
 ll = torch.empty(b, dtype=torch.float64, device=dev)
 nobs = torch.empty(b, dtype=torch.int32, device=dev)
