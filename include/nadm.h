@@ -43,7 +43,7 @@ extern "C" {
 #define NADM_MAX_K 64
 #define NADM_MAX_BUCKETS 8
 #define NADM_MAX_P2_SLICES 8   /* sample slices of pass 2 (nadm_decode_bce_sliced) */
-#define NADM_ABI_VERSION 14  /* 14: nadm_clock_probe; new symbols only, same version: nadm_plan_set_precision / nadm_plan_precision (NADM_PRECISION_*), nadm_class_sums + NADM_LABEL_NONE (labels in [-1, k)), nadm_project_q / nadm_project_scratch_floats (projection: Q refined against a fixed P); 13: pass 3 in sample slices (nadm_encode_bwd_sliced, nadm_encode_slices(_max), nadm_encode_slab_floats, nadm_encode_bwd_chunks, nadm_plan_desc_t.p3_slab / p3_cnt); 12: nadm_test_force_slices / nadm_test_force_generic_mlp exist in the test build only (-DNADM_TEST_HOOKS), nadm_calib_clock / nadm_wall_clock_khz; 11: nadm_gmm_fit_means_dev, nadm_loglik_blocks counts 8 row slices per 1024-SNP block, nadm_decode_bce_sliced / nadm_decode_slices / nadm_decode_slab_floats / nadm_test_force_slices + nadm_plan_desc_t.p2_slab / p2_cnt (pass 2 in sample slices when the SNP chunks alone do not fill the chip); 10: message B of the sample-sharded step in SNP-range buckets (nadm_flat_layout takes n_buckets, nadm_flat_layout_t.bkt_*, nadm_plan_desc_t.n_buckets / p3_whole / comm_a / debug, nadm_encode_fwd_part, nadm_plan_bucket_ms), nadm_comm_t.async_error, nadm_comm_rccl_probe, nadm_comm_rccl with a watchdog (timeout_ms), a failed step poisons its plan; 9: nadm_step / nadm_plan_* / nadm_comm_* / nadm_flat_layout (the step as one call, sharded optimizer), nadm_test_force_generic_mlp; 8: nadm_dz_image(_bytes), nadm_mlp_bwd_image; nadm_encode_bwd, nadm_encode_bwd_step, nadm_pca_project_t take the operand image of dZ / Y; 7: nadm_encode_fwd_step, nadm_sum_rows, dqpart of nadm_mlp_bwd is float* (folded in place); 6: nadm_mlp_fwd_images, nadm_decode_bce_images, nadm_q_image_bytes, nadm_encode_fwd_small; 5: nadm_adam_t.when, nadm_adam2, with_loss bit 1; 4: nadm_decode_bce_step, nadm_encode_bwd_step (nadm_adam_t, nadm_mlp_weights_t), nadm_small_grads; 3: nadm_decode_bce_gather; 2: nadm_mlp_bwd_weights, nadm_supervised_ce, nadm_pca_project(_t), nadm_loglik, nadm_savetxt_f32, nadm_decode_chunk_snps; grad_small of nadm_mlp_bwd may be NULL */
+#define NADM_ABI_VERSION 14  /* 14: nadm_clock_probe; new symbols only, same version: nadm_plan_set_precision / nadm_plan_precision (NADM_PRECISION_*), nadm_class_sums + NADM_LABEL_NONE (labels in [-1, k)), nadm_project_q / nadm_project_scratch_floats (projection: Q refined against a fixed P), nadm_snp_counts / nadm_ld_band / nadm_select_snps / nadm_ld_sweep (LD pruning); 13: pass 3 in sample slices (nadm_encode_bwd_sliced, nadm_encode_slices(_max), nadm_encode_slab_floats, nadm_encode_bwd_chunks, nadm_plan_desc_t.p3_slab / p3_cnt); 12: nadm_test_force_slices / nadm_test_force_generic_mlp exist in the test build only (-DNADM_TEST_HOOKS), nadm_calib_clock / nadm_wall_clock_khz; 11: nadm_gmm_fit_means_dev, nadm_loglik_blocks counts 8 row slices per 1024-SNP block, nadm_decode_bce_sliced / nadm_decode_slices / nadm_decode_slab_floats / nadm_test_force_slices + nadm_plan_desc_t.p2_slab / p2_cnt (pass 2 in sample slices when the SNP chunks alone do not fill the chip); 10: message B of the sample-sharded step in SNP-range buckets (nadm_flat_layout takes n_buckets, nadm_flat_layout_t.bkt_*, nadm_plan_desc_t.n_buckets / p3_whole / comm_a / debug, nadm_encode_fwd_part, nadm_plan_bucket_ms), nadm_comm_t.async_error, nadm_comm_rccl_probe, nadm_comm_rccl with a watchdog (timeout_ms), a failed step poisons its plan; 9: nadm_step / nadm_plan_* / nadm_comm_* / nadm_flat_layout (the step as one call, sharded optimizer), nadm_test_force_generic_mlp; 8: nadm_dz_image(_bytes), nadm_mlp_bwd_image; nadm_encode_bwd, nadm_encode_bwd_step, nadm_pca_project_t take the operand image of dZ / Y; 7: nadm_encode_fwd_step, nadm_sum_rows, dqpart of nadm_mlp_bwd is float* (folded in place); 6: nadm_mlp_fwd_images, nadm_decode_bce_images, nadm_q_image_bytes, nadm_encode_fwd_small; 5: nadm_adam_t.when, nadm_adam2, with_loss bit 1; 4: nadm_decode_bce_step, nadm_encode_bwd_step (nadm_adam_t, nadm_mlp_weights_t), nadm_small_grads; 3: nadm_decode_bce_gather; 2: nadm_mlp_bwd_weights, nadm_supervised_ce, nadm_pca_project(_t), nadm_loglik, nadm_savetxt_f32, nadm_decode_chunk_snps; grad_small of nadm_mlp_bwd may be NULL */
 
 /* Head table shared by the MLP entry points (mirror of NeuralEncoder/NeuralDecoder's ks list,
  * neural_admixture.py:27-29,66-76). Offsets are element offsets into the `small` flat buffer. */
@@ -607,6 +607,52 @@ int64_t nadm_kinship_scratch_floats(int32_t ba, int32_t bb, int64_t M);
 int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
                  const float* P, int32_t k, int32_t kp, const float* QA, const float* QB, int32_t q_stride, float pimin,
                  double* num, double* den, int32_t* nobs, float* scratch, void* stream);
+
+/* ---- LD pruning: windowed r^2 of neighbouring SNPs on the matrix pipe, and the keep-list ---------------------------------------
+ * ADMIXTURE-type models assume SNPs in linkage equilibrium; the usual preparation is plink's --indep-pairwise.  These entries do it
+ * on the packed matrix already in HBM.  Codes g in {0, 1, 2} are observed, 3 is missing; o = 1 where a call is observed, else 0.
+ * Rows: idx[0..rows) (idx == NULL: rows 0..rows; any order, a duplicate counts as often as it occurs), rows in 1..2^24.
+ *
+ * nadm_snp_counts: per SNP j < M over those rows, cnt[j] = { n_obs = sum o, sum g o, sum g^2 o } (int32 [M, 3], zeroed here).  A
+ * plain vector kernel, row slices added with integer atomics: exact, the same bits whatever the order.
+ *
+ * nadm_ld_band: entry (j - m0, d) of r2 [m1 - m0, W] (and of mom [m1 - m0, W, 6], which may be NULL) is the pair
+ * (a, b) = (j, j + 1 + d) for m0 <= j < m1, 0 <= d < W.  The six moments, over the rows where BOTH calls are observed (every term
+ * is masked to 0 where its own call is missing):
+ *     n   = sum o_a o_b        Sa  = sum g_a o_b        Sb  = sum o_a g_b
+ *     Sab = sum g_a g_b        Saa = sum g_a^2 o_b      Sbb = sum o_a g_b^2
+ * and, in int64,   cov = n Sab - Sa Sb,   va = n Saa - Sa^2,   vb = n Sbb - Sb^2,
+ *     r2 = ((double)cov * (double)cov) / ((double)va * (double)vb)        (two products and a division, each one IEEE operation)
+ * r2 is exactly 0.0 where va == 0, vb == 0 or b >= M; the moments are 0 where b >= M.  rows <= 2^24 keeps cov, va, vb below 2^53.
+ * The products run on the matrix pipe (v_mfma_i32_16x16x64_i8, samples on its k axis): per side a SNP enters as the three int8
+ * pieces o in {0,1}, g o in {0,1,2} and g^2 o in {0,1,4}; the sums are int32 and EXACT (at most 4 rows <= 2^26).  The pad bits of
+ * a row's last byte, rows beyond `rows` and SNPs >= M enter as exactly 0.  Integer sums: the same inputs give the same bits, no
+ * floating-point atomics, no scratch.  W in 1..NADM_LD_MAX_WINDOW, 0 <= m0 < m1 <= M.
+ * Both: ld >= ceil(M/4), ld % 16 == 0, ld < 2^32; xp 16-byte, idx / cnt / mom 4-byte, r2 8-byte aligned.
+ *
+ * nadm_select_snps: out[r, j'] = the code of xp[r, keep[j']] for r < rows, j' < M_out; flip != 0 exchanges the codes 0 and 2 (3
+ * stays 3).  keep int64 [M_out] on the device, ascending, values in [0, M_in) (M_in <= 4 ld_in: the caller's; a value outside the
+ * row is not followed); out [rows, ld_out], ld_out >= ceil(M_out/4), the row padding is written as zeros.  keep 8-byte aligned.
+ *
+ * Every refusal of the three is reported before anything is launched.  Asynchronous on `stream`.
+ *
+ * nadm_ld_sweep (host code, synchronous, no GPU): the greedy pass that turns the band of [m0, m1) into removals.  r2 [m1 - m0, W]
+ * as written by nadm_ld_band (host copy), maf double [M], chrom int32 [M] (may be NULL: one chromosome), kept uint8 [M] in/out:
+ *     for i = m0 .. m1 - 1 ascending, if kept[i]:
+ *       for d = 0 .. W - 1 ascending, j = i + 1 + d < M:
+ *         stop at the first j with chrom[j] != chrom[i];  skip a j with kept[j] == 0;
+ *         if r2[i - m0, d] > thr: remove the SNP with the smaller maf -- j on a tie; if i was removed, go on with the next i.
+ * Calls over consecutive ranges [m0, m1) with the same `kept` equal ONE call over [0, M): the caller holds one range of the band
+ * at a time.  maf_j = min(S, 2 n - S) / (2.0 n) from nadm_snp_counts (n = n_obs, S = sum g o), 0 where n = 0.  This is plink's
+ * --indep-pairwise with a step of 1 and without its window bookkeeping; plink's list is not promised. */
+#define NADM_LD_MAX_WINDOW 1024
+int nadm_snp_counts(const uint8_t* xp, int64_t ld, const int32_t* idx, int64_t rows, int64_t M, int32_t* cnt, void* stream);
+int nadm_ld_band(const uint8_t* xp, int64_t ld, const int32_t* idx, int64_t rows, int64_t M, int64_t m0, int64_t m1, int32_t W,
+                 double* r2, int32_t* mom, void* stream);
+int nadm_select_snps(const uint8_t* xp, int64_t ld_in, int64_t rows, const int64_t* keep, int64_t M_out, int32_t flip,
+                     uint8_t* out, int64_t ld_out, void* stream);
+int nadm_ld_sweep(const double* r2, int64_t m0, int64_t m1, int32_t W, int64_t M, const double* maf, const int32_t* chrom,
+                  double thr, uint8_t* kept);
 
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,

@@ -110,6 +110,10 @@ def _load():
         "nadm_kinship_ranges": (i32, [i32, i32, i64]),
         "nadm_kinship_scratch_floats": (i64, [i32, i32, i64]),
         "nadm_kinship": (C.c_int, [vp, i64, vp, i32, vp, i32, i64, vp, i32, i32, vp, vp, i32, f32, vp, vp, vp, vp, vp]),
+        "nadm_snp_counts": (C.c_int, [vp, i64, vp, i64, i64, vp, vp]),
+        "nadm_ld_band": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp]),
+        "nadm_select_snps": (C.c_int, [vp, i64, i64, vp, i64, i32, vp, i64, vp]),
+        "nadm_ld_sweep": (C.c_int, [vp, i64, i64, i32, i64, vp, vp, C.c_double, vp]),
         "nadm_savetxt_f32": (C.c_int, [C.c_char_p, vp, i64, i64, i64]),
         "nadm_gmm_fit_means": (C.c_int, [vp, i64, i32, i32, vp, i32, C.c_double, i32, C.c_double, vp, C.POINTER(C.c_double), C.POINTER(i32)]),
         "nadm_gmm_fit_means_dev": (C.c_int, [vp, i64, i32, i32, vp, i32, C.c_double, i32, C.c_double, vp, C.POINTER(C.c_double), C.POINTER(i32), vp]),

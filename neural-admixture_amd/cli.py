@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -25,6 +25,12 @@ def _add_precision(p):
     p.add_argument("--precision", choices=("highest", "medium"), default="highest",
                    help="matmul precision of the genotype passes: 'highest' (fp32-class products, default) or 'medium' (bf16-class, "
                         "what the reference's torch.set_float32_matmul_precision('medium') gives)")
+
+
+def _add_extract(p):
+    p.add_argument("--extract", type=str, default=None, metavar="FILE",
+                   help="use only the SNPs whose IDs (column 2 of the .bim) FILE lists, one per line -- a {name}.prune.in of the 'prune' "
+                        "mode, or any list plink --extract would read.  BED input only.  Default: every SNP")
 
 
 def parse_train_args(argv):
@@ -70,6 +76,7 @@ def parse_train_args(argv):
     p.add_argument("--polish_tol", type=float, default=1e-5,
                    help="stop polishing once no entry of Q or P moves by this much in a round")
     _add_precision(p)
+    _add_extract(p)
     return p.parse_args(argv)
 
 
@@ -90,6 +97,7 @@ def parse_infer_args(argv):
     p.add_argument("--refine_tol", type=float, default=1e-4,
                    help="stop refining a batch once no entry of Q moves by this much in a step")
     _add_precision(p)
+    _add_extract(p)
     return p.parse_args(argv)
 
 
@@ -106,7 +114,92 @@ def parse_kinship_args(argv):
     p.add_argument("--pimin", type=float, default=0.0,
                    help="drop a call whose individual-specific allele frequency is outside [pimin, 1 - pimin] (default 0: every observed call counts)")
     p.add_argument("--threads", type=int, default=1)
+    _add_extract(p)
     return p.parse_args(argv)
+
+
+def parse_prune_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture prune",
+                                description="LD pruning: the SNPs to keep so that no two within a window have an r^2 above a threshold")
+    p.add_argument("--data_path", required=True, type=str)
+    p.add_argument("--save_dir", required=True, type=str)
+    p.add_argument("--name", required=True, type=str)
+    p.add_argument("--window", type=int, default=50, help="a SNP is compared with its next window - 1 neighbours on its chromosome (default 50)")
+    p.add_argument("--r2", type=float, default=0.1, help="of a pair with an r^2 above this the SNP with the smaller minor-allele frequency goes (default 0.1)")
+    p.add_argument("--threads", type=int, default=1)
+    return p.parse_args(argv)
+
+
+def _bed_shape(data_path):
+    """(N, M, .bim path) of a BED input from the .fam file and the size of the .bed, without reading a genotype; a missing file or a
+    .bed that does not hold whole SNPs ends the run, naming it."""
+    from pathlib import Path
+    base = Path(data_path)
+    bim, fam, bed = base.with_suffix(".bim"), base.with_suffix(".fam"), base.with_suffix(".bed")
+    for f in (bim, fam, bed):
+        if not f.is_file():
+            raise SystemExit(f"    {f} not found.")
+    with open(fam) as fb:
+        n = sum(1 for _ in fb)
+    nb = (n + 3) // 4
+    if n < 1 or (bed.stat().st_size - 3) < nb or (bed.stat().st_size - 3) % nb:
+        raise SystemExit(f"    {bed} does not hold whole SNPs of the {n} samples of {fam}.")
+    return n, (bed.stat().st_size - 3) // nb, bim
+
+
+def _extract_keep(data_path, extract):
+    """--extract FILE -> bool [M] over the SNPs of the .bim, before any genotype is read; None without the flag.  VCF input, an unknown
+    ID and a listed ID that the .bim holds twice end the run, naming the offender."""
+    if not extract:
+        return None
+    from . import ld
+    name = os.path.basename(data_path)
+    if ".vcf" in name:
+        raise SystemExit("    --extract resolves SNP IDs through a .bim file: it is not available for VCF input.")
+    if ".bed" not in name:
+        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
+    if not os.path.isfile(extract):
+        raise SystemExit(f"    {extract} not found.")
+    _, m, bim = _bed_shape(data_path)
+    ids, _ = ld.read_bim(bim)
+    if len(ids) != m:
+        raise SystemExit(f"    {bim} lists {len(ids)} SNPs, the .bed holds {m}.")
+    keep = ld.resolve_ids(ids, ld.read_id_list(extract), str(bim), extract)
+    log.info(f"    --extract: {int(keep.sum())} of {m} SNPs.")
+    return keep
+
+
+def _prune_main(argv, t0):
+    """``prune`` mode: {save_dir}/{name}.prune.in and .prune.out, the kept and the removed SNP IDs of the .bim, one per line in file
+    order (readable by plink --extract and by --extract here)."""
+    from . import ld
+    args = parse_prune_args(argv)
+    if args.window < 2 or args.window > ld.MAX_WINDOW:
+        raise SystemExit(f"    --window must be in 2..{ld.MAX_WINDOW}.")
+    if not 0.0 <= args.r2 <= 1.0:
+        raise SystemExit("    --r2 must be in [0, 1].")
+    name = os.path.basename(args.data_path)
+    if ".vcf" in name:
+        raise SystemExit("    prune needs the SNP IDs and chromosomes of a .bim file: it is not available for VCF input.")
+    if ".bed" not in name:
+        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed.")
+    n, m, bim = _bed_shape(args.data_path)                  # before the GPU check and before any genotype is read
+    ids, chroms = ld.read_bim(bim)
+    if len(ids) != m:
+        raise SystemExit(f"    {bim} lists {len(ids)} SNPs, the .bed holds {m}.")
+    if not torch.cuda.is_available():
+        raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
+    torch.set_num_threads(max(1, args.threads))
+    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True)
+    keep, stats = ld.prune(data.packed, data.M, args.window, args.r2, chrom=ld.chrom_codes(chroms))
+    os.makedirs(args.save_dir, exist_ok=True)
+    ld.write_id_list(os.path.join(args.save_dir, f"{args.name}.prune.in"), [s for s, k in zip(ids, keep) if k])
+    ld.write_id_list(os.path.join(args.save_dir, f"{args.name}.prune.out"), [s for s, k in zip(ids, keep) if not k])
+    log.info(f"    LD pruning (window {args.window}, r2 {args.r2:g}): {stats['kept']} SNPs kept, {stats['removed']} removed "
+             f"({stats['seconds']:.2f} seconds; {stats['ranges']} ranges).")
+    log.info("    SNP lists saved.")
+    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
+    return 0
 
 
 def _kinship_main(argv, t0):
@@ -127,6 +220,7 @@ def _kinship_main(argv, t0):
         raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
     P_path = find_P_files(args.save_dir, args.name, [args.k], what="kinship")[0]   # before anything is read
     Q_path = relate.find_Q_files(args.save_dir, args.name, [args.k])[0]
+    keep = _extract_keep(args.data_path, args.extract)     # (the .P then has one row per listed SNP)
     n_known = m_known = None
     if ".bed" in name:                                      # the .fam file and the size of the .bed give N and M without reading a genotype
         from pathlib import Path
@@ -139,7 +233,7 @@ def _kinship_main(argv, t0):
         nb = (n_known + 3) // 4
         if n_known < 1 or (bed.stat().st_size - 3) < nb or (bed.stat().st_size - 3) % nb:
             raise SystemExit(f"    {bed} does not hold whole SNPs of the {n_known} samples of {fam}.")
-        m_known = (bed.stat().st_size - 3) // nb
+        m_known = (bed.stat().st_size - 3) // nb if keep is None else int(keep.sum())
     # both files are read and checked before the genotypes: the widths always, the row counts where the input tells N and M up front
     # (.bed); a VCF's are known only once it is parsed, and are checked then
     Q = relate.read_matrix_file(Q_path, args.k, n_known)
@@ -147,7 +241,7 @@ def _kinship_main(argv, t0):
     if not torch.cuda.is_available():
         raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
     torch.set_num_threads(max(1, args.threads))
-    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True)
+    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
     for path, a, rows in ((Q_path, Q, data.N), (P_path, P, data.M)):
         if a.shape[0] != rows:
             raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the data needs {rows} x {args.k}.")
@@ -169,7 +263,9 @@ def _kinship_main(argv, t0):
     return 0
 
 
-def _read(path, device=None, keep_on_device=False):
+def _read(path, device=None, keep_on_device=False, keep=None):
+    """The genotypes as PackedGenotypes; ``keep`` (bool per SNP of the file, from --extract: BED input only) selects SNPs right after
+    the read, and everything downstream sees an ordinary PackedGenotypes of the kept ones."""
     from .io import read_bed_packed, read_vcf_packed
     name = os.path.basename(path)
     if ".vcf" in name:                                   # src/snp_reader.py:103
@@ -183,6 +279,10 @@ def _read(path, device=None, keep_on_device=False):
     log.info("    Input format is BED.")
     data = read_bed_packed(path, device, keep_on_device)
     log.info(f"    Data contains {data.N} samples and {data.M} SNPs.")
+    if keep is not None:
+        from .ld import select_snps
+        data = select_snps(data, keep)
+        log.info(f"    Using the {data.M} SNPs of --extract.")
     return data
 
 
@@ -217,10 +317,12 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "kinship"), 'Please provide either the argument "train" or "infer" to choose running mode.'
+    assert argv and argv[0] in ("train", "infer", "kinship", "prune"), 'Please provide either the argument "train" or "infer" to choose running mode.'
     mode, t0 = argv[0], time.time()
     if mode == "kinship":                                   # (its argument and file checks come before the GPU check)
         return _kinship_main(argv[1:], t0)
+    if mode == "prune":                                     # (likewise)
+        return _prune_main(argv[1:], t0)
     if not torch.cuda.is_available():
         raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
     if mode == "train":
@@ -251,7 +353,8 @@ def main(argv=None):
         torch.set_num_threads(max(1, args.threads))          # ... this process's pools are already up: torch here, BLAS / OpenMP
                                                              # through train(host_threads=) (threadpoolctl)
         from .svd import RSVD
-        data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=(num_gpus == 1))   # 2-bit transpose on the GPU
+        keep = _extract_keep(args.data_path, args.extract)  # before any genotype is read
+        data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=(num_gpus == 1), keep=keep)   # 2-bit transpose on the GPU
         log.info("")
         log.info("    Running SVD...")
         V = RSVD(data, data.N, data.M, args.n_components, args.seed)
@@ -264,6 +367,7 @@ def main(argv=None):
     args = parse_infer_args(argv[1:])
     from .model import Q_P
     from .io import write_outputs
+    keep = _extract_keep(args.data_path, args.extract)      # before anything is loaded
     with open(f"{args.save_dir}/{args.name}_config.json") as fb:
         cfg = json.load(fb)
     Ps = None
@@ -277,7 +381,7 @@ def main(argv=None):
     if args.precision != "highest":
         log.info(f"    Matmul precision: {args.precision} (bf16-class products in the genotype passes).")
     model.load_state_dict(sd, device=torch.device("cuda:0"), max_batch=args.batch_size, precision=args.precision)
-    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True)
+    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
     eng = model.engine
     eng.pack_from_host(data)
     idx = torch.arange(data.N, dtype=torch.int32, device=eng.device)

@@ -12,16 +12,18 @@ hipcc $FLAGS -c nadm_calib.hip -o nadm_calib.o "$@"             # measurement he
 hipcc $FLAGS -c nadm_project.hip -o nadm_project.o "$@"         # projection: Q refined against a fixed P (nadm_project_q; not on the training path)
 hipcc $FLAGS -c nadm_project_p.hip -o nadm_project_p.o "$@"     # the other half: P refitted against a fixed Q (nadm_project_p; not on the training path)
 hipcc $FLAGS -c nadm_kinship.hip -o nadm_kinship.o "$@"         # admixture-aware kinship from Q and P on the matrix pipe (nadm_kinship; not on the training path)
+hipcc $FLAGS -c nadm_ld.hip -o nadm_ld.o "$@"                   # LD pruning: windowed r^2 on the matrix pipe, SNP counts, SNP selection (not on the training path)
 # host-only units, compiled as plain C++ (no device pass)
 hipcc $HOST -c nadm_gmm.cpp -o nadm_gmm.o "$@"                  # decoder-init mixture fit on the host
 hipcc $HOST -c nadm_host_io.cpp -o nadm_host_io.o "$@"          # host packer, .bed converter, VCF parser, savetxt
 hipcc $HOST -c nadm_layout.cpp -o nadm_layout.o "$@"            # head table + flat parameter layout
+hipcc $HOST -c nadm_ld_sweep.cpp -o nadm_ld_sweep.o "$@"        # the greedy sweep of LD pruning
 # the test hooks (nadm_test_force_slices / _p3_slices / _generic_mlp) are the one difference between the two libraries: nadm_hooks.cpp
 # without the macro has no setter and getters that return 0; with it, the setters exist.  Every other object, the kernels included, is
 # linked into both.  The tests that need a hook re-run themselves in a child process against the TEST build (tests/conftest.py: in_hook_build).
 hipcc $HOST -c nadm_hooks.cpp -o nadm_hooks.o "$@"
 hipcc $HOST -DNADM_TEST_HOOKS -c nadm_hooks.cpp -o nadm_hooks_th.o "$@"
-OBJS="nadm_genotype_passes.o nadm_small_kernels.o nadm_step.o nadm_gmm.o nadm_gmm_dev.o nadm_calib.o nadm_project.o nadm_project_p.o nadm_kinship.o nadm_host_io.o nadm_layout.o"
+OBJS="nadm_genotype_passes.o nadm_small_kernels.o nadm_step.o nadm_gmm.o nadm_gmm_dev.o nadm_calib.o nadm_project.o nadm_project_p.o nadm_kinship.o nadm_ld.o nadm_host_io.o nadm_layout.o nadm_ld_sweep.o"
 hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-soname,libnadm.so -o libnadm.so $OBJS nadm_hooks.o -lpthread -ldl
 echo "built $(pwd)/libnadm.so"
 hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-soname,libnadm.so -o libnadm_testhooks.so $OBJS nadm_hooks_th.o -lpthread -ldl
