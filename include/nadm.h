@@ -654,6 +654,39 @@ int nadm_select_snps(const uint8_t* xp, int64_t ld_in, int64_t rows, const int64
 int nadm_ld_sweep(const double* r2, int64_t m0, int64_t m1, int32_t W, int64_t M, const double* maf, const int32_t* chrom,
                   double thr, uint8_t* kept);
 
+/* ---- Hardy-Weinberg proportions given ancestry: the per-SNP score test of an inbreeding coefficient ----------------------------
+ * The likelihood itself is the model's third assumption: a genotype is binomial(2, pi_ij), i.e. Hardy-Weinberg proportions GIVEN the
+ * sample's ancestry.  SNPs that break it (heterozygote drop-out, paralogs, batch effects) bias P and Q; plink's plain --hwe rejects
+ * good SNPs of a structured panel through the Wahlund effect.  One call = the rows idx[0..b) (idx == NULL: rows 0..b; any order, a
+ * duplicate counts as often as it occurs), Q [b, k] (row s belongs to idx[s], row stride q_stride, a multiple of 4, >= kp, pad cols
+ * 0) and ONE head P [M, kp] (kp = nadm_pad_k(k), pad cols 0).  Codes g in {0, 1, 2} are observed, 3 is missing:
+ *     pi_ij  = sum_k q_ik p_jk                                      (fp32, fused multiply-adds, k in order, as nadm_kinship)
+ *     m_ij   = 1 if the call is observed, j < M and pimin <= pi_ij <= 1 - pimin (1 - pimin rounded to fp32), else 0
+ *     r = clip(pi, eps, 1 - eps);   u = clip(1 - pi, eps, 1 - eps)  (u from the UNCLIPPED pi, as nadm_project_p)
+ *     t_ij   = r / u if g = 0;   -1 if g = 1;   u / r if g = 2
+ *     U_j    = sum_i m_ij t_ij                  Hexp_j = sum_i m_ij 2 pi_ij (1 - pi_ij)
+ *     n_j    = sum_i m_ij                       Hobs_j = sum_i m_ij [g_ij == 1]
+ * t is the score of a per-SNP inbreeding coefficient F at F = 0 in P(g = 0) = (1 - pi)^2 + F pi (1 - pi), P(g = 1) = 2 pi (1 - pi)
+ * (1 - F), P(g = 2) = pi^2 + F pi (1 - pi): E t = 0 and Var t = 1 for every pi, and the cross information of F with pi is 0.  The
+ * caller forms Z_j = U_j / sqrt(n_j) (N(0, 1) under the model, positive: excess homozygotes), F_j = U_j / n_j and 1 - Hobs_j /
+ * Hexp_j; the only divisions by sums are the caller's.  U, Hexp double [M], nobs, Hobs int32 [M]; Hexp and Hobs may be NULL.
+ * eps in [1e-9, 0.5), pimin in [0, 0.5) (t is heavy-tailed for pi near 0 or 1: pimin is the guard).  scratch:
+ * nadm_snp_hwe_scratch_floats(b, M) floats (grows with b and with M).  xp, Q, P, scratch 16-byte, U, Hexp 8-byte, nobs, Hobs, idx
+ * 4-byte aligned; ld >= ceil(M/4), ld % 16 == 0, ld < 2^32.
+ * A missing call, a row past the list, a SNP >= M and a masked pi enter every sum as exactly +0.0f / 0 (the result does not depend
+ * on the pad bits of a row's last byte, nor on P at a SNP nobody observes).  t is num * rcp(den) with the hardware's 1-ulp
+ * reciprocal.  The batch's 64-sample tiles are cut into nadm_snp_hwe_slices(b, M) slices of whole tiles (1 for b <= 64; more while
+ * M alone does not fill the chip; never more than 4096 samples in one slice): U and Hexp are fp32 sums within a slice in sample
+ * order, the slices' partials are added in float64 in slice order; n and Hobs are integer sums, exact.  The order depends on (b, M)
+ * alone and there are no floating-point atomics: the same inputs give the same bits.  Every refusal is reported before anything is
+ * launched. */
+int32_t nadm_snp_hwe_slices(int32_t b, int64_t M);
+int64_t nadm_snp_hwe_scratch_floats(int32_t b, int64_t M);
+int nadm_snp_hwe(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                 const float* Q, int32_t q_stride, int32_t k, int32_t kp, const float* P,
+                 float eps, float pimin, double* U, double* Hexp, int32_t* nobs, int32_t* Hobs,
+                 float* scratch, void* stream);
+
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,
  * random_state=seed).fit(X).means_): the EM iterations of that call in float64 on the host (csrc/nadm_gmm.cpp restates the

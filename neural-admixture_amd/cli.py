@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -130,6 +130,24 @@ def parse_prune_args(argv):
     return p.parse_args(argv)
 
 
+def parse_hwe_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture hwe",
+                                description="Hardy-Weinberg test given ancestry: a per-SNP score test from a run's .P and .Q files")
+    p.add_argument("--data_path", required=True, type=str)
+    p.add_argument("--save_dir", required=True, type=str)
+    p.add_argument("--name", required=True, type=str)
+    p.add_argument("--k", required=True, type=int)
+    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
+    p.add_argument("--pimin", type=float, default=0.0,
+                   help="drop a call whose individual-specific allele frequency is outside [pimin, 1 - pimin] (default 0: every observed "
+                        "call counts); the score is heavy-tailed for rare variants, 0.01 to 0.05 guards against that")
+    p.add_argument("--alpha", type=float, default=1e-6,
+                   help="a SNP whose two-sided p-value is below this goes to the .hwe.out list (default 1e-6, plink's customary --hwe threshold)")
+    p.add_argument("--threads", type=int, default=1)
+    _add_extract(p)
+    return p.parse_args(argv)
+
+
 def _bed_shape(data_path):
     """(N, M, .bim path) of a BED input from the .fam file and the size of the .bed, without reading a genotype; a missing file or a
     .bed that does not hold whole SNPs ends the run, naming it."""
@@ -198,6 +216,58 @@ def _prune_main(argv, t0):
     log.info(f"    LD pruning (window {args.window}, r2 {args.r2:g}): {stats['kept']} SNPs kept, {stats['removed']} removed "
              f"({stats['seconds']:.2f} seconds; {stats['ranges']} ranges).")
     log.info("    SNP lists saved.")
+    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
+    return 0
+
+
+def _hwe_main(argv, t0):
+    """``hwe`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.hwe (``id n het_obs het_exp F Z p`` per SNP in
+    file order) and {out_name}.{k}.hwe.in / .hwe.out, the kept and the removed SNP IDs (readable by --extract)."""
+    from . import hwe, ld, relate
+    from .project import find_P_files, read_P_files
+    args = parse_hwe_args(argv)
+    if args.k < 1 or args.k > 64:
+        raise SystemExit("    --k must be in 1..64.")
+    if not 0.0 <= args.pimin < 0.5:
+        raise SystemExit("    --pimin must be in [0, 0.5).")
+    if not 0.0 < args.alpha <= 1.0:
+        raise SystemExit("    --alpha must be in (0, 1].")
+    name = os.path.basename(args.data_path)
+    if ".vcf" in name:
+        raise SystemExit("    hwe needs the SNP IDs of a .bim file: it is not available for VCF input.")
+    if ".bed" not in name:
+        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed.")
+    P_path = find_P_files(args.save_dir, args.name, [args.k], what="hwe")[0]       # before anything is read
+    Q_path = relate.find_Q_files(args.save_dir, args.name, [args.k], what="hwe")[0]
+    n, m, bim = _bed_shape(args.data_path)                  # before the GPU check and before any genotype is read
+    ids, _ = ld.read_bim(bim)
+    if len(ids) != m:
+        raise SystemExit(f"    {bim} lists {len(ids)} SNPs, the .bed holds {m}.")
+    keep = _extract_keep(args.data_path, args.extract)     # (the .P then has one row per listed SNP)
+    if keep is not None:
+        ids = [s for s, k in zip(ids, keep) if k]
+    Q = relate.read_matrix_file(Q_path, args.k, n)
+    P = read_P_files([P_path], [args.k], len(ids))[0]
+    if not torch.cuda.is_available():
+        raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
+    torch.set_num_threads(max(1, args.threads))
+    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
+    res = hwe.snp_hwe(data.packed, data.M, P, Q, pimin=args.pimin)
+    kept = hwe.hwe_keep(res.p, args.alpha, res.n)
+    out = args.out_name or args.name
+    os.makedirs(args.save_dir, exist_ok=True)
+    hwe.write_table(os.path.join(args.save_dir, f"{out}.{args.k}.hwe"), ids, res)
+    ld.write_id_list(os.path.join(args.save_dir, f"{out}.{args.k}.hwe.in"), [s for s, k in zip(ids, kept) if k])
+    ld.write_id_list(os.path.join(args.save_dir, f"{out}.{args.k}.hwe.out"), [s for s, k in zip(ids, kept) if not k])
+    Z = res.Z.cpu().numpy()
+    Z = Z[~np.isnan(Z)]
+    med, sd = (float(np.median(Z)), float(np.std(Z))) if len(Z) else (float("nan"), float("nan"))
+    log.info(f"    Hardy-Weinberg test given ancestry (pimin {args.pimin:g}): {len(Z)} of {len(ids)} SNPs tested, "
+             f"{int((~kept).sum())} removed at p < {args.alpha:g}.")
+    log.info(f"    Z over the tested SNPs: median {med:.3f}, standard deviation {sd:.3f} (the model expects 0 and 1).")
+    if sd > 1.2:
+        log.info(f"    Warning: the standard deviation of Z is {sd:.2f}; K may be too small or the panel related.")
+    log.info("    Test table and SNP lists saved.")
     log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
     return 0
 
@@ -317,12 +387,15 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "kinship", "prune"), 'Please provide either the argument "train" or "infer" to choose running mode.'
+    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe"), \
+        'Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions).'
     mode, t0 = argv[0], time.time()
     if mode == "kinship":                                   # (its argument and file checks come before the GPU check)
         return _kinship_main(argv[1:], t0)
     if mode == "prune":                                     # (likewise)
         return _prune_main(argv[1:], t0)
+    if mode == "hwe":                                       # (likewise)
+        return _hwe_main(argv[1:], t0)
     if not torch.cuda.is_available():
         raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
     if mode == "train":

@@ -594,6 +594,25 @@ class Engine:
         Q = torch.cat([self.infer_q(seq[s:s + self.bmax], min(self.bmax, N - s))[head] for s in range(0, N, self.bmax)], dim=0)
         return relate.kinship_pairs(self.xp, L.M, self.P(head), Q, relate.MIN_PHI if min_phi is None else min_phi, pimin=pimin)
 
+    def snp_hwe(self, head: int = 0, pimin: float = 0.0):
+        """Hardy-Weinberg proportions given ancestry, per SNP of the resident matrix, from head ``head``'s P and the encoder's final
+        Q (hwe.snp_hwe; include/nadm.h, nadm_snp_hwe): an ``HweResult`` with ``Z, F, Fhet, p`` (float64), ``n, Hobs`` (int32) and
+        ``Hexp`` (float64) ``[M]``.  A check of the likelihood the model assumes; the engine's parameters and optimiser state are
+        left as they are."""
+        from . import hwe
+        if self.mode != "single" or self.world != 1:
+            raise NotImplementedError("Engine.snp_hwe is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
+                                      "P; use hwe.snp_hwe on one GPU from the written .P and .Q files instead")
+        if self._plan is None or self.xp is None:
+            raise RuntimeError("Engine.snp_hwe needs the HIP engine with its packed matrix resident (no CPU fallback)")
+        L = self.lay
+        if not 0 <= head < len(L.ks):
+            raise RuntimeError(f"Engine.snp_hwe: head must be in 0..{len(L.ks) - 1}")
+        N = int(self.xp.shape[0])
+        seq = torch.arange(N, dtype=torch.int32, device=self.device)
+        Q = torch.cat([self.infer_q(seq[s:s + self.bmax], min(self.bmax, N - s))[head] for s in range(0, N, self.bmax)], dim=0)
+        return hwe.snp_hwe(self.xp, L.M, self.P(head), Q, pimin=pimin)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()

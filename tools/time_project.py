@@ -13,7 +13,12 @@ four alike); a timed window is 10 back-to-back calls.  Reported: the median per 
     python tools/time_project.py --kinship [--b 1024] [--M 500000] [--K 8] [--rounds 10] [--out profiles/kinship.txt]
 The kinship leg (nadm_kinship, relate.py): one b x b block of sample pairs at M SNPs next to a plain torch formulation of the same block
 on the same GPU (per slab of 16384 SNPs: unpack, pi = Q.P^T, the mask, d and s in fp32, then D.D^T, S.S^T and m.m^T as fp32 matmuls --
-in this tool only), and the whole pair list of the configs[1] shape (2504 x 600k) through relate.kinship_pairs."""
+in this tool only), and the whole pair list of the configs[1] shape (2504 x 600k) through relate.kinship_pairs.
+
+    python tools/time_project.py --hwe [--b 100000] [--M 500000] [--K 8] [--rounds 10] [--out profiles/snp_hwe.txt]
+The Hardy-Weinberg leg (nadm_snp_hwe, hwe.py): the four per-SNP sums over b resident rows (all of them, in a permuted order) next to
+a plain torch fp32 formulation of the same sums on the same GPU (per block of 8192 rows x 16384 SNPs: unpack, pi = Q.P^T, the mask, the
+clips, t and 2 pi (1 - pi) elementwise, column sums -- in this tool only)."""
 import argparse
 import ctypes as C
 import sys
@@ -33,15 +38,18 @@ ap.add_argument("--rounds", type=int, default=30)
 ap.add_argument("--calls", type=int, default=10)
 ap.add_argument("--out", default=None)
 ap.add_argument("--kinship", action="store_true", help="the kinship leg instead of the projection groups")
+ap.add_argument("--hwe", action="store_true", help="the Hardy-Weinberg leg instead of the projection groups")
 a = ap.parse_args()
 if a.out is None:
-    a.out = "profiles/kinship.txt" if a.kinship else "profiles/project_p.txt"
+    a.out = "profiles/kinship.txt" if a.kinship else ("profiles/snp_hwe.txt" if a.hwe else "profiles/project_p.txt")
 if a.b is None:
-    a.b = 1024 if a.kinship else 800
+    a.b = 1024 if a.kinship else (100_000 if a.hwe else 800)
+if a.hwe and a.rounds == 30:
+    a.rounds = 10
 assert torch.cuda.is_available(), "time_project.py measures on the GPU; there is no fallback"
 dev = torch.device("cuda:0")
 b, M, K = a.b, a.M, a.K
-kp, ld, rows = int(lib.nadm_pad_k(K)), ModelLayout.row_stride(M), 4 * b
+kp, ld, rows = int(lib.nadm_pad_k(K)), ModelLayout.row_stride(M), (b if a.hwe else 4 * b)
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 rng = np.random.default_rng(1)
 Fq = torch.from_numpy(np.clip(0.5 * rng.beta(0.5, 0.5, size=(K, M)), 0.005, 0.5).astype(np.float32)).to(dev)
@@ -132,8 +140,81 @@ def kinship_leg():
         fb.write(text)
 
 
+def hwe_leg():
+    eps, pimin = 1e-6, 0.0
+    U, Hexp = torch.empty(M, dtype=torch.float64, device=dev), torch.empty(M, dtype=torch.float64, device=dev)
+    nn, Hobs = torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, dtype=torch.int32, device=dev)
+    h_scratch = torch.empty(int(lib.nadm_snp_hwe_scratch_floats(b, M)), dtype=torch.float32, device=dev)
+
+    def hip():
+        check(lib.nadm_snp_hwe(ptr(xp), ld, ptr(idx), b, M, ptr(Q), kp, K, kp, ptr(P), eps, pimin, ptr(U), ptr(Hexp), ptr(nn), ptr(Hobs),
+                               ptr(h_scratch), st), "snp_hwe")
+
+    rblock, slab = 8192, 16384
+    shifts = torch.tensor([0, 2, 4, 6], dtype=torch.uint8, device=dev)
+    rows_l = idx.long()
+
+    def plain(with_abs=False):
+        U_, H_ = torch.zeros(M, dtype=torch.float32, device=dev), torch.zeros(M, dtype=torch.float32, device=dev)
+        n_, o_ = torch.zeros(M, dtype=torch.int32, device=dev), torch.zeros(M, dtype=torch.int32, device=dev)
+        T_ = torch.zeros(M, dtype=torch.float32, device=dev)
+        for r0 in range(0, b, rblock):
+            r1 = min(b, r0 + rblock)
+            for j0 in range(0, M, slab):
+                j1 = min(M, j0 + slab)
+                by = xp[rows_l[r0:r1], j0 // 4:(j1 + 3) // 4]
+                code = ((by[:, :, None] >> shifts) & 3).reshape(by.shape[0], -1)[:, :j1 - j0]
+                pi = Q[r0:r1, :K] @ P[j0:j1, :K].T
+                m = (code != 3) & (pi >= pimin) & (pi <= 1.0 - pimin)
+                r, u = torch.clamp(pi, eps, 1.0 - eps), torch.clamp(1.0 - pi, eps, 1.0 - eps)
+                t = torch.where(code == 0, r / u, torch.where(code == 2, u / r, torch.full_like(pi, -1.0))) * m
+                U_[j0:j1] += t.sum(dim=0)
+                H_[j0:j1] += (2.0 * pi * (1.0 - pi) * m).sum(dim=0)
+                n_[j0:j1] += m.sum(dim=0, dtype=torch.int32)
+                o_[j0:j1] += (m & (code == 1)).sum(dim=0, dtype=torch.int32)
+                if with_abs:
+                    T_[j0:j1] += t.abs().sum(dim=0)
+        return U_, H_, n_, o_, T_
+
+    hip()
+    want = plain(with_abs=True)
+    hip()
+    plain()
+    torch.cuda.synchronize()
+    agree_u = float(((U - want[0].double()).abs() / want[4].double().clamp(min=1e-30)).max())
+    agree_h = float(((Hexp - want[1].double()).abs() / want[1].double().clamp(min=1e-30)).max())
+    same_n = bool(torch.equal(nn, want[2]) and torch.equal(Hobs, want[3]))
+    t = {"nadm_snp_hwe": [], "torch fp32": []}
+    for _ in range(a.rounds):
+        for name, f in (("nadm_snp_hwe", hip), ("torch fp32", plain)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            t[name].append(e0.elapsed_time(e1))
+    q = {n: np.percentile(v, [25, 50, 75]) for n, v in t.items()}
+    cells = float(b) * M
+    lines = [f"tools/time_project.py --hwe: b = {b} resident rows (permuted gather list), M = {M}, K = {K} (kp = {kp}), ld = {ld}; {torch.cuda.get_device_name(0)}",
+             f"device events, {a.rounds} rounds, the two alternating; ms per call: median [quartiles]"]
+    for n in t:
+        lines.append(f"  {n:13s} {q[n][1]:10.3f}  [{q[n][0]:.3f}, {q[n][2]:.3f}]   {cells / q[n][1] / 1e6:.1f} G genotypes/s")
+    lines.append(f"  nadm_snp_hwe / torch fp32 = {q['nadm_snp_hwe'][1] / q['torch fp32'][1]:.4f}; {int(lib.nadm_snp_hwe_slices(b, M))} sample slice(s), "
+                 f"partials {4 * h_scratch.numel() / 1e6:.1f} MB; packed matrix {b * ld / 1e9:.2f} GB once through HBM = "
+                 f"{b * ld / q['nadm_snp_hwe'][1] / 1e9:.3f} TB/s at that time")
+    lines.append(f"  against the torch sums: max |U - U_torch| / T_abs = {agree_u:.2e}, max |Hexp - Hexp_torch| / Hexp = {agree_h:.2e}, "
+                 f"n and Hobs {'equal' if same_n else 'DIFFER'}")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    with open(a.out, "w") as fb:
+        fb.write(text)
+
+
 if a.kinship:
     kinship_leg()
+    sys.exit(0)
+if a.hwe:
+    hwe_leg()
     sys.exit(0)
 Qo = torch.empty_like(Q)
 ll = torch.empty(b, dtype=torch.float64, device=dev)
