@@ -32,6 +32,42 @@ __device__ __forceinline__ uint32_t lt_mask64(int64_t a, int64_t b) {  // the sa
 }
 __device__ __forceinline__ float keepf(float x, uint32_t m) { return __uint_as_float(__float_as_uint(x) & m); }
 __device__ __forceinline__ uint32_t blend(uint32_t if_set, uint32_t if_clear, uint32_t m) { return (if_set & m) | (if_clear & ~m); }   // v_bfi_b32
+// x >= 0 ? ~0 : 0 from the sign bit (a NaN or -0.0f goes by its sign bit; x = a - b of finite a != b is never -0.0f, a == b gives +0.0f)
+__device__ __forceinline__ uint32_t ge0_mask(float x) {
+    uint32_t m = ~(uint32_t)((int)__float_as_uint(x) >> 31);
+    asm("" : "+v"(m));
+    return m;
+}
+// 2-bit call observed (code != 3) ? ~0 : 0, as arithmetic on the code; opaque, so that LLVM does not fold it back into compare + select
+__device__ __forceinline__ uint32_t obs_mask(uint32_t code) {
+    uint32_t m = ((code + 1u) >> 2) - 1u;
+    asm("" : "+v"(m));
+    return m;
+}
+
+// ---- vectors of four dwords (one 16-byte load or store, one MFMA operand or accumulator) ---------
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+
+// ---- the clipped terms of one genotype in a masked EM step of the binomial admixture model (projection of Q and of P) ----
+// rr = q . p unclipped, code the call, m = obs_mask(code).  r and u = 1 - r are clipped to [eps, 1 - eps], u from the UNCLIPPED
+// product: 1 - fl(1 - eps) is 1.3 % off eps in fp32, which a row of P = 1 would carry into the log-likelihood.
+// t1 = g / r and t0 = (2 - g) / u; a masked call gives exactly +0.0f in both.
+struct EmTerms {
+    float r, u, g, h, t1, t0;
+};
+__device__ __forceinline__ EmTerms em_terms(float rr, uint32_t code, uint32_t m, float eps, float one_m_eps) {
+    EmTerms e;
+    e.r = fminf(fmaxf(rr, eps), one_m_eps);
+    e.u = fminf(fmaxf(1.f - rr, eps), one_m_eps);
+    e.g = (float)code;
+    e.h = 2.f - e.g;
+    e.t1 = keepf(e.g * __builtin_amdgcn_rcpf(e.r), m);
+    e.t0 = keepf(e.h * __builtin_amdgcn_rcpf(e.u), m);
+    return e;
+}
 
 // ---- wave64 reductions with DPP (no LDS traffic) -------------------------------------------
 template <int CTRL, int ROW_MASK = 0xf>

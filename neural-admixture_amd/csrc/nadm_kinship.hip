@@ -26,16 +26,6 @@ constexpr int KIN_STEP = 32;              // SNPs per build / multiply step = K 
 constexpr int KIN_MAX_CHUNKS = 1024;      // chunks per range at most: no fp32 accumulator covers more than 2^18 SNPs (n exact: < 2^24)
 constexpr int64_t KIN_BLOCKS = 512;       // blocks wanted at least (256 CUs x 2 blocks of 4 waves), while there are chunks to split
 constexpr int KIN_PIECES = 5;             // d_hi, d_lo, s_hi, s_lo, m
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
-// x >= 0 ? ~0 : 0 from the sign bit (a NaN or -0.0f goes by its sign bit; x = a - b of finite a != b is never -0.0f, a == b gives +0.0f)
-__device__ __forceinline__ uint32_t ge0_mask(float x) {
-    uint32_t m = ~(uint32_t)((int)__float_as_uint(x) >> 31);
-    asm("" : "+v"(m));
-    return m;
-}
 
 template <int KP>
 __global__ __launch_bounds__(256, KP <= 16 ? 2 : 1) void kinship_accum_kernel(
@@ -131,9 +121,7 @@ __global__ __launch_bounds__(256, KP <= 16 ? 2 : 1) void kinship_accum_kernel(
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const uint32_t code = (bits >> (2 * e)) & 3u;
-                    // observed ? ~0 : 0 as arithmetic on the code, applied with v_and (nadm_common.h: no select on a lane condition)
-                    uint32_t m = ((code + 1u) >> 2) - 1u;
-                    asm("" : "+v"(m));
+                    uint32_t m = obs_mask(code);
                     m &= svalid & lt_mask(e, rem) & ge0_mask(pi[e] - pimin) & ge0_mask(one_m_pimin - pi[e]);
                     mv[e] = m;
                     dv[e] = keepf((float)code - 2.f * pi[e], m);
@@ -220,15 +208,12 @@ __global__ __launch_bounds__(256) void kinship_fold_kernel(const float* __restri
 static int64_t kin_chunks(int64_t M) { return (M + KIN_CHUNK - 1) / KIN_CHUNK; }
 static int64_t kin_tiles(int ba, int bb) { return (int64_t)((ba + KIN_TILE - 1) / KIN_TILE) * ((bb + KIN_TILE - 1) / KIN_TILE); }
 
-// chunks per range, a rule of (ba, bb, M) alone: as many ranges as it takes to put KIN_BLOCKS blocks on the chip while there are
-// chunks to split, and never more than KIN_MAX_CHUNKS chunks in one range
+// chunks per range, a rule of (ba, bb, M) alone: the split rule of nadm_host.h over the chunk axis
 static int64_t kin_chunks_per_range(int ba, int bb, int64_t M) {
-    const int64_t tiles = kin_tiles(ba, bb), chunks = kin_chunks(M);
-    int64_t want = (KIN_BLOCKS + tiles - 1) / tiles;
-    if (want > chunks) want = chunks;
-    const int64_t least = (chunks + KIN_MAX_CHUNKS - 1) / KIN_MAX_CHUNKS;
-    if (want < least) want = least;
-    return (chunks + want - 1) / want;
+    return split_per_part(kin_chunks(M), kin_tiles(ba, bb), KIN_BLOCKS, KIN_MAX_CHUNKS);
+}
+static bool kin_shape_ok(int ba, int bb, int64_t M) {
+    return ba > 0 && bb > 0 && ba <= NADM_KINSHIP_MAX_ROWS && bb <= NADM_KINSHIP_MAX_ROWS && M > 0;
 }
 
 }  // namespace nadm
@@ -236,21 +221,16 @@ static int64_t kin_chunks_per_range(int ba, int bb, int64_t M) {
 using namespace nadm;
 
 extern "C" int32_t nadm_kinship_ranges(int32_t ba, int32_t bb, int64_t M) {
-    if (ba <= 0 || bb <= 0 || ba > NADM_KINSHIP_MAX_ROWS || bb > NADM_KINSHIP_MAX_ROWS || M <= 0) return 0;
+    if (!kin_shape_ok(ba, bb, M)) return 0;
     const int64_t cpr = kin_chunks_per_range(ba, bb, M);
     const int64_t r = (kin_chunks(M) + cpr - 1) / cpr;
     return r > 0x7FFFFFFFll ? 0 : (int32_t)r;
 }
 
-// scratch: [ranges][tiles][num | den | n][64 x 64] float.  Sized by a bound of tiles x ranges that grows with ba, bb and M (the
-// product itself does not: ceil(512 / tiles) tiles wobbles with tiles)
+// scratch: [ranges][tiles][num | den | n][64 x 64] float
 extern "C" int64_t nadm_kinship_scratch_floats(int32_t ba, int32_t bb, int64_t M) {
-    if (ba <= 0 || bb <= 0 || ba > NADM_KINSHIP_MAX_ROWS || bb > NADM_KINSHIP_MAX_ROWS || M <= 0) return 0;
-    const int64_t tiles = kin_tiles(ba, bb), chunks = kin_chunks(M);
-    const int64_t least = (chunks + KIN_MAX_CHUNKS - 1) / KIN_MAX_CHUNKS;
-    int64_t blocks = tiles * chunks < KIN_BLOCKS - 1 + tiles ? tiles * chunks : KIN_BLOCKS - 1 + tiles;
-    if (blocks < tiles * least) blocks = tiles * least;
-    return blocks * (3 * KIN_TILE * KIN_TILE);
+    if (!kin_shape_ok(ba, bb, M)) return 0;
+    return split_blocks_bound(kin_chunks(M), kin_tiles(ba, bb), KIN_BLOCKS, KIN_MAX_CHUNKS) * (3 * KIN_TILE * KIN_TILE);
 }
 
 extern "C" int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
@@ -259,12 +239,7 @@ extern "C" int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, 
     if (!xp || !P || !QA || !QB || !num || !den || !scratch) return fail("nadm_kinship: null pointer");
     if (ba <= 0 || bb <= 0 || M <= 0) return fail("nadm_kinship: empty block (need ba > 0, bb > 0 and M > 0)");
     if (ba > NADM_KINSHIP_MAX_ROWS || bb > NADM_KINSHIP_MAX_ROWS) return fail("nadm_kinship: ba and bb must be <= NADM_KINSHIP_MAX_ROWS");
-    if (ld * 4 < M) return fail("nadm_kinship: ld < ceil(M/4)");
-    if (ld % 16 != 0 || ld >= (1ll << 32)) return fail("nadm_kinship: ld must be a multiple of 16 and < 2^32");
-    if (k < 1 || k > NADM_MAX_K) return fail("nadm_kinship: K must be in 1..NADM_MAX_K");
-    if (kp != nadm_pad_k(k)) return fail("nadm_kinship: kp must be nadm_pad_k(k)");
-    if (q_stride < kp) return fail("nadm_kinship: q_stride < kp");
-    if (q_stride % 4 != 0) return fail("nadm_kinship: q_stride must be a multiple of 4");
+    if (check_packed("nadm_kinship", ld, M) || check_head("nadm_kinship", k, kp, q_stride)) return 1;
     if (!(pimin >= 0.f && pimin < 0.5f)) return fail("nadm_kinship: pimin must be in [0, 0.5)");
     if ((((uintptr_t)xp | (uintptr_t)P | (uintptr_t)QA | (uintptr_t)QB | (uintptr_t)scratch) & 15) != 0)
         return fail("nadm_kinship: xp, P, QA, QB and scratch must be 16-byte aligned");
@@ -278,17 +253,11 @@ extern "C" int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, 
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(tiles * ranges);
     const float ome = 1.f - pimin;
-#define NADM_KIN_CASE(KP)                                                                                                              \
-    case KP:                                                                                                                           \
-        hipLaunchKernelGGL((kinship_accum_kernel<KP>), dim3(grid), dim3(256), 0, st, xp, ld, idxA, ba, idxB, bb, M, P, QA, QB, q_stride, \
-                           pimin, ome, tiles_b, (int)ranges, (int)cpr, chunks, scratch);                                               \
-        break;
-    switch (kp) {
-        NADM_KIN_CASE(4) NADM_KIN_CASE(8) NADM_KIN_CASE(12) NADM_KIN_CASE(16)
-        NADM_KIN_CASE(24) NADM_KIN_CASE(32) NADM_KIN_CASE(48) NADM_KIN_CASE(64)
-        default: return fail("nadm_kinship: unsupported padded K (use nadm_pad_k)");
-    }
-#undef NADM_KIN_CASE
+    if (int e = dispatch_kp("nadm_kinship", kp, [&](auto KP) {
+            hipLaunchKernelGGL((kinship_accum_kernel<decltype(KP)::value>), dim3(grid), dim3(256), 0, st, xp, ld, idxA, ba, idxB, bb, M, P, QA,
+                               QB, q_stride, pimin, ome, tiles_b, (int)ranges, (int)cpr, chunks, scratch);
+        }))
+        return e;
     if (int e = check_launch("kinship (accumulate)")) return e;
     hipLaunchKernelGGL(kinship_fold_kernel, dim3((unsigned)(((int64_t)ba * bb + 255) / 256)), dim3(256), 0, st, scratch, (int)ranges,
                        (int)tiles, tiles_b, ba, bb, num, den, nobs);

@@ -30,8 +30,6 @@ constexpr int LD_BT = LD_NBG + 3;         // "b" tiles of the image: wave 3's la
 constexpr int LD_SNPS = LD_TA + 16 * LD_BT;        // SNP rows of the operand image (240)
 constexpr int LD_ROW = 80;                // bytes per image row: 64 samples + 16 (a dword column of four SNP groups then spreads over the banks)
 constexpr int LD_RAWC = 64;               // byte columns of the transposed stage: 16 of "a", 48 of "b"
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256, 2) void ld_band_kernel(const uint8_t* __restrict__ xp, const int64_t ld, const int32_t* __restrict__ idx,
                                                          const int rows, const int64_t M, const int64_t m0, const int64_t m1, const int W,
@@ -224,13 +222,12 @@ __global__ __launch_bounds__(256) void select_snps_kernel(const uint8_t* __restr
     }
 }
 
-static int ld_common_checks(const char* who, const void* xp, int64_t ld, const int32_t* idx, int64_t rows, int64_t M, char* msg) {
-    if (rows < 1 || rows > (1ll << 24)) { snprintf(msg, 256, "%s: rows must be in 1..2^24", who); return 1; }
-    if (M < 1) { snprintf(msg, 256, "%s: M must be >= 1", who); return 1; }
-    if (ld * 4 < M) { snprintf(msg, 256, "%s: ld < ceil(M/4)", who); return 1; }
-    if (ld % 16 != 0 || ld >= (1ll << 32)) { snprintf(msg, 256, "%s: ld must be a multiple of 16 and < 2^32", who); return 1; }
-    if (((uintptr_t)xp & 15) != 0) { snprintf(msg, 256, "%s: xp must be 16-byte aligned", who); return 1; }
-    if (((uintptr_t)idx & 3) != 0) { snprintf(msg, 256, "%s: idx must be 4-byte aligned", who); return 1; }
+static int ld_common_checks(const char* who, const void* xp, int64_t ld, const int32_t* idx, int64_t rows, int64_t M) {
+    if (rows < 1 || rows > (1ll << 24)) return failf(who, "rows must be in 1..2^24");
+    if (M < 1) return failf(who, "M must be >= 1");
+    if (check_packed(who, ld, M)) return 1;
+    if (((uintptr_t)xp & 15) != 0) return failf(who, "xp must be 16-byte aligned");
+    if (((uintptr_t)idx & 3) != 0) return failf(who, "idx must be 4-byte aligned");
     return 0;
 }
 
@@ -240,8 +237,7 @@ using namespace nadm;
 
 extern "C" int nadm_snp_counts(const uint8_t* xp, int64_t ld, const int32_t* idx, int64_t rows, int64_t M, int32_t* cnt, void* stream) {
     if (!xp || !cnt) return fail("nadm_snp_counts: null pointer");
-    char msg[256];
-    if (ld_common_checks("nadm_snp_counts", xp, ld, idx, rows, M, msg)) return fail(msg);
+    if (ld_common_checks("nadm_snp_counts", xp, ld, idx, rows, M)) return 1;
     if (((uintptr_t)cnt & 3) != 0) return fail("nadm_snp_counts: cnt must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(cnt, 0, (size_t)M * 3 * sizeof(int32_t), st) != hipSuccess) return fail("nadm_snp_counts: hipMemsetAsync failed");
@@ -261,8 +257,7 @@ extern "C" int nadm_snp_counts(const uint8_t* xp, int64_t ld, const int32_t* idx
 extern "C" int nadm_ld_band(const uint8_t* xp, int64_t ld, const int32_t* idx, int64_t rows, int64_t M, int64_t m0, int64_t m1, int32_t W,
                             double* r2, int32_t* mom, void* stream) {
     if (!xp || !r2) return fail("nadm_ld_band: null pointer");
-    char msg[256];
-    if (ld_common_checks("nadm_ld_band", xp, ld, idx, rows, M, msg)) return fail(msg);
+    if (ld_common_checks("nadm_ld_band", xp, ld, idx, rows, M)) return 1;
     if (W < 1 || W > NADM_LD_MAX_WINDOW) return fail("nadm_ld_band: W must be in 1..NADM_LD_MAX_WINDOW");
     if (m0 < 0 || m0 >= m1 || m1 > M) return fail("nadm_ld_band: need 0 <= m0 < m1 <= M");
     if (((uintptr_t)r2 & 7) != 0 || ((uintptr_t)mom & 3) != 0) return fail("nadm_ld_band: r2 must be 8-byte and mom 4-byte aligned");

@@ -81,10 +81,7 @@ __global__ __launch_bounds__(PROJ_TILE) void project_accum_kernel(
 #pragma unroll 4
             for (int t = 0; t < 16; ++t) {
                 const uint32_t code = (bits >> (2 * t)) & 3u;
-                // observed ? ~0 : 0 as arithmetic on the code and applied with v_and (selects on a lane condition are the slow
-                // VCC form of v_cndmask, nadm_common.h); opaque, so that LLVM does not fold it back into compare + select
-                uint32_t m = ((code + 1u) >> 2) - 1u;
-                asm("" : "+v"(m));
+                const uint32_t m = obs_mask(code);
                 const float* pr = Ps + (wd * 16 + t) * KP;
                 float p[KP];
 #pragma unroll
@@ -95,18 +92,13 @@ __global__ __launch_bounds__(PROJ_TILE) void project_accum_kernel(
                 float rr = 0.f;
 #pragma unroll
                 for (int k = 0; k < KP; ++k) rr = fmaf(q[k], p[k], rr);
-                // 1 - r from the UNCLIPPED product: 1 - fl(1 - eps) is 1.3 % off eps in fp32, which a row of P = 1 would carry into ll
-                const float r = fminf(fmaxf(rr, eps), one_m_eps);
-                const float u = fminf(fmaxf(1.f - rr, eps), one_m_eps);
-                const float g = (float)code, h = 2.f - g;
-                const float t1 = keepf(g * __builtin_amdgcn_rcpf(r), m);      // masked: exactly +0.0f
-                const float t0 = keepf(h * __builtin_amdgcn_rcpf(u), m);
+                const EmTerms e = em_terms(rr, code, m, eps, one_m_eps);
                 // both terms as they stand: (1 - p_jk) / (1 - r_j) <= 1 / q_k however small 1 - r_j gets, whereas the cheaper
                 // sum_j t0_j + sum_j p_jk (t1_j - t0_j) cancels two sums of ~1/eps when a row of P is all ones
 #pragma unroll
-                for (int k = 0; k < KP; ++k) a[k] = fmaf(1.f - p[k], t0, fmaf(p[k], t1, a[k]));
+                for (int k = 0; k < KP; ++k) a[k] = fmaf(1.f - p[k], e.t0, fmaf(p[k], e.t1, a[k]));
                 n += (int)(m & 1u);
-                if constexpr (WITH_LL) llw += keepf(g * __log2f(r) + h * __log2f(u), m);      // v_log_f32; ln 2 once per word
+                if constexpr (WITH_LL) llw += keepf(e.g * __log2f(e.r) + e.h * __log2f(e.u), m);      // v_log_f32; ln 2 once per word
             }
             if constexpr (WITH_LL) ll += llw * 0.693147180559945f;
         }
@@ -192,13 +184,7 @@ extern "C" int nadm_project_q(const uint8_t* xp, int64_t ld, const int32_t* idx,
                               float* scratch, void* stream) {
     if (!xp || !P || !Qin || !Qout || !scratch) return fail("nadm_project_q: null pointer");
     if (b <= 0 || M <= 0) return fail("nadm_project_q: empty batch (need b > 0 and M > 0)");
-    if (ld * 4 < M) return fail("nadm_project_q: ld < ceil(M/4)");
-    if (ld % 16 != 0 || ld >= (1ll << 32)) return fail("nadm_project_q: ld must be a multiple of 16 and < 2^32");
-    if (k < 1 || k > NADM_MAX_K) return fail("nadm_project_q: K must be in 1..NADM_MAX_K");
-    if (kp != nadm_pad_k(k)) return fail("nadm_project_q: kp must be nadm_pad_k(k)");
-    if (q_stride < kp) return fail("nadm_project_q: q_stride < kp");
-    if (q_stride % 4 != 0) return fail("nadm_project_q: q_stride must be a multiple of 4");
-    if (!(eps >= 1e-9f && eps < 0.5f)) return fail("nadm_project_q: eps must be in [1e-9, 0.5)");
+    if (check_packed("nadm_project_q", ld, M) || check_head("nadm_project_q", k, kp, q_stride) || check_eps("nadm_project_q", eps)) return 1;
     if (!(qmin >= 0.f && qmin < 1.f)) return fail("nadm_project_q: qmin must be in [0, 1)");
     if ((((uintptr_t)xp | (uintptr_t)P | (uintptr_t)Qin | (uintptr_t)Qout | (uintptr_t)scratch) & 15) != 0)
         return fail("nadm_project_q: xp, P, Qin, Qout and scratch must be 16-byte aligned");
@@ -211,14 +197,10 @@ extern "C" int nadm_project_q(const uint8_t* xp, int64_t ld, const int32_t* idx,
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(chunks * tiles);
     const bool wl = loglik != nullptr;
-#define NADM_PROJ_CASE(KP) \
-    case KP: launch_accum<KP>(wl, grid, st, xp, ld, idx, b, M, P, Qin, q_stride, eps, tiles, apart, npart, llpart); break;
-    switch (kp) {
-        NADM_PROJ_CASE(4) NADM_PROJ_CASE(8) NADM_PROJ_CASE(12) NADM_PROJ_CASE(16)
-        NADM_PROJ_CASE(24) NADM_PROJ_CASE(32) NADM_PROJ_CASE(48) NADM_PROJ_CASE(64)
-        default: return fail("nadm_project_q: unsupported padded K (use nadm_pad_k)");
-    }
-#undef NADM_PROJ_CASE
+    if (int e = dispatch_kp("nadm_project_q", kp, [&](auto KP) {
+            launch_accum<decltype(KP)::value>(wl, grid, st, xp, ld, idx, b, M, P, Qin, q_stride, eps, tiles, apart, npart, llpart);
+        }))
+        return e;
     if (int e = check_launch("project_q (accumulate)")) return e;
     hipLaunchKernelGGL(project_fold_kernel, dim3((unsigned)b), dim3(64), 0, st, apart, npart, llpart, chunks, b, k, kp, Qin, Qout, q_stride, qmin,
                        loglik, nobs);

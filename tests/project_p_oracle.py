@@ -10,7 +10,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import project_oracle as R  # noqa: E402
 
-SLICE = 64           # samples per fp32 partial sum of the float32 restatement (= the kernel's tile, csrc/nadm_project_p.hip)
+SLICE = 64           # samples per fp32 partial sum of the float32 restatement (= the kernel's tile, csrc/nadm_snp_sweep.h: SWEEP_TILE)
 EPS = R.EPS
 PMIN = 1e-6
 

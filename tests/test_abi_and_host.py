@@ -145,6 +145,26 @@ def test_pass3_sample_slice_rule_and_slab_sizes():
     assert chunks == 123 and lib.nadm_encode_slab_floats(62_500, 8, 2) == 2 * chunks * 512 * 8 and lib.nadm_encode_slab_floats(62_500, 8, 1) == 0
 
 
+def test_split_schedule_of_the_analysis_kernels_is_the_recorded_one():
+    """The slices, ranges and scratch sizes of project_q, project_p, snp_hwe and kinship are pure host rules of the shape.  Their values
+    over the grid of the schedule tests, and the argument lists that must return 0, were recorded (tests/golden/split_schedule.json)
+    from the library in which every entry point carried its own copy of the split rule; the shared rule (csrc/nadm_host.h:
+    split_per_part, split_blocks_bound) returns every one of them unchanged."""
+    import itertools
+    from neural_admixture_amd._lib import lib
+    rec = json.load(open(os.path.join(G, "split_schedule.json")))
+    names = [n for n in rec if not n.startswith("_")]
+    assert sorted(names) == sorted(["nadm_project_p_slices", "nadm_project_p_scratch_floats", "nadm_snp_hwe_slices", "nadm_snp_hwe_scratch_floats",
+                                    "nadm_kinship_ranges", "nadm_kinship_scratch_floats", "nadm_project_scratch_floats"])
+    for name in names:
+        fn, r = getattr(lib, name), rec[name]
+        points = list(itertools.product(*[vals for _, vals in r["axes"]]))
+        assert len(points) == len(r["values"]) and any(r["values"])
+        got = [int(fn(*a)) for a in points]
+        assert got == r["values"], (name, [(a, g, w) for a, g, w in zip(points, got, r["values"]) if g != w][:5])
+        assert r["invalid"] and all(int(fn(*a)) == 0 for a in r["invalid"]), name
+
+
 def test_force_hook_of_the_test_build_overrides_the_slice_rule(request):
     from conftest import in_hook_build
     if not in_hook_build(request):

@@ -21,7 +21,7 @@ import project_oracle as R  # noqa: E402
 import project_p_oracle as PO  # noqa: E402
 
 G = os.path.join(os.path.dirname(__file__), "golden")
-PP_CHUNK = 256               # SNPs per chunk of the accumulate kernel (csrc/nadm_project_p.hip: PP_CHUNK); 64-sample tiles
+PP_CHUNK = 256               # SNPs per chunk of the accumulate kernel (csrc/nadm_snp_sweep.h: SWEEP_CHUNK); 64-sample tiles
 ROWS = 200                   # resident rows of the GPU cases
 GRID = [(b, M, K) for b in (1, 70, 130, 200) for M in (257, 513, 1027, 3001) for K in (2, 3, 8, 9, 16, 20)]
 BIG = (4200, 257, 8)         # crosses the 4096 samples one fp32 running sum may cover
