@@ -17,6 +17,9 @@ import time
 import numpy as np
 import torch
 
+from .engine import row_ranges
+from .io import chrom_codes, find_run_files, read_bim, read_id_list, read_run_matrix, resolve_ids, write_id_list
+
 logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(message)s")
 log = logging.getLogger(__name__)
 
@@ -148,13 +151,34 @@ def parse_hwe_args(argv):
     return p.parse_args(argv)
 
 
-def _bed_shape(data_path):
-    """(N, M, .bim path) of a BED input from the .fam file and the size of the .bed, without reading a genotype; a missing file or a
-    .bed that does not hold whole SNPs ends the run, naming it."""
+def _need_gpu():
+    if not torch.cuda.is_available():
+        raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
+
+
+def _check_k_pimin(args):
+    if args.k < 1 or args.k > 64:
+        raise SystemExit("    --k must be in 1..64.")
+    if not 0.0 <= args.pimin < 0.5:
+        raise SystemExit("    --pimin must be in [0, 0.5).")
+
+
+def _need_bed(data_path, why, formats=".bed"):
+    """Ends the run unless the input is a BED: a VCF with ``why`` (what needs a .bim), anything else naming ``formats``."""
+    name = os.path.basename(data_path)
+    if ".vcf" in name:
+        raise SystemExit(f"    {why}: it is not available for VCF input.")
+    if ".bed" not in name:
+        raise SystemExit(f"    Invalid format. Unrecognized file format. Make sure file ends with {formats}.")
+
+
+def _bed_shape(data_path, need_bim=True):
+    """(N, M, .bim path) of a BED input from the .fam file and the size of the .bed, without reading a genotype; a missing file (the
+    .bim only with ``need_bim``) or a .bed that does not hold whole SNPs ends the run, naming it."""
     from pathlib import Path
     base = Path(data_path)
     bim, fam, bed = base.with_suffix(".bim"), base.with_suffix(".fam"), base.with_suffix(".bed")
-    for f in (bim, fam, bed):
+    for f in (bim, fam, bed) if need_bim else (fam, bed):
         if not f.is_file():
             raise SystemExit(f"    {f} not found.")
     with open(fam) as fb:
@@ -165,26 +189,41 @@ def _bed_shape(data_path):
     return n, (bed.stat().st_size - 3) // nb, bim
 
 
+def _bed_ids(data_path):
+    """(N, M, .bim path, SNP IDs, chromosome labels) of a BED input, before any genotype is read: ``_bed_shape`` and a .bim with one
+    line per SNP of the .bed."""
+    n, m, bim = _bed_shape(data_path)
+    ids, chroms = read_bim(bim)
+    if len(ids) != m:
+        raise SystemExit(f"    {bim} lists {len(ids)} SNPs, the .bed holds {m}.")
+    return n, m, bim, ids, chroms
+
+
 def _extract_keep(data_path, extract):
     """--extract FILE -> bool [M] over the SNPs of the .bim, before any genotype is read; None without the flag.  VCF input, an unknown
     ID and a listed ID that the .bim holds twice end the run, naming the offender."""
     if not extract:
         return None
-    from . import ld
-    name = os.path.basename(data_path)
-    if ".vcf" in name:
-        raise SystemExit("    --extract resolves SNP IDs through a .bim file: it is not available for VCF input.")
-    if ".bed" not in name:
-        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
+    _need_bed(data_path, "--extract resolves SNP IDs through a .bim file", ".bed or .vcf")
     if not os.path.isfile(extract):
         raise SystemExit(f"    {extract} not found.")
-    _, m, bim = _bed_shape(data_path)
-    ids, _ = ld.read_bim(bim)
-    if len(ids) != m:
-        raise SystemExit(f"    {bim} lists {len(ids)} SNPs, the .bed holds {m}.")
-    keep = ld.resolve_ids(ids, ld.read_id_list(extract), str(bim), extract)
+    _, m, bim, ids, _ = _bed_ids(data_path)
+    keep = resolve_ids(ids, read_id_list(extract), str(bim), extract)
     log.info(f"    --extract: {int(keep.sum())} of {m} SNPs.")
     return keep
+
+
+def _read_on_gpu(args, keep=None):
+    """What an analysis mode does once its arguments and files are in order: the GPU check, the host threads, the genotypes in HBM."""
+    _need_gpu()
+    torch.set_num_threads(max(1, args.threads))
+    return _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
+
+
+def _write_id_lists(stem, ids, keep):
+    """``{stem}.in`` and ``{stem}.out``: the kept and the removed SNP IDs, one per line in the order given."""
+    write_id_list(f"{stem}.in", [s for s, k in zip(ids, keep) if k])
+    write_id_list(f"{stem}.out", [s for s, k in zip(ids, keep) if not k])
 
 
 def _prune_main(argv, t0):
@@ -196,23 +235,12 @@ def _prune_main(argv, t0):
         raise SystemExit(f"    --window must be in 2..{ld.MAX_WINDOW}.")
     if not 0.0 <= args.r2 <= 1.0:
         raise SystemExit("    --r2 must be in [0, 1].")
-    name = os.path.basename(args.data_path)
-    if ".vcf" in name:
-        raise SystemExit("    prune needs the SNP IDs and chromosomes of a .bim file: it is not available for VCF input.")
-    if ".bed" not in name:
-        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed.")
-    n, m, bim = _bed_shape(args.data_path)                  # before the GPU check and before any genotype is read
-    ids, chroms = ld.read_bim(bim)
-    if len(ids) != m:
-        raise SystemExit(f"    {bim} lists {len(ids)} SNPs, the .bed holds {m}.")
-    if not torch.cuda.is_available():
-        raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
-    torch.set_num_threads(max(1, args.threads))
-    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True)
-    keep, stats = ld.prune(data.packed, data.M, args.window, args.r2, chrom=ld.chrom_codes(chroms))
+    _need_bed(args.data_path, "prune needs the SNP IDs and chromosomes of a .bim file")
+    _, _, _, ids, chroms = _bed_ids(args.data_path)         # before the GPU check and before any genotype is read
+    data = _read_on_gpu(args)
+    keep, stats = ld.prune(data.packed, data.M, args.window, args.r2, chrom=chrom_codes(chroms))
     os.makedirs(args.save_dir, exist_ok=True)
-    ld.write_id_list(os.path.join(args.save_dir, f"{args.name}.prune.in"), [s for s, k in zip(ids, keep) if k])
-    ld.write_id_list(os.path.join(args.save_dir, f"{args.name}.prune.out"), [s for s, k in zip(ids, keep) if not k])
+    _write_id_lists(os.path.join(args.save_dir, f"{args.name}.prune"), ids, keep)
     log.info(f"    LD pruning (window {args.window}, r2 {args.r2:g}): {stats['kept']} SNPs kept, {stats['removed']} removed "
              f"({stats['seconds']:.2f} seconds; {stats['ranges']} ranges).")
     log.info("    SNP lists saved.")
@@ -223,42 +251,27 @@ def _prune_main(argv, t0):
 def _hwe_main(argv, t0):
     """``hwe`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.hwe (``id n het_obs het_exp F Z p`` per SNP in
     file order) and {out_name}.{k}.hwe.in / .hwe.out, the kept and the removed SNP IDs (readable by --extract)."""
-    from . import hwe, ld, relate
-    from .project import find_P_files, read_P_files
+    from . import hwe
     args = parse_hwe_args(argv)
-    if args.k < 1 or args.k > 64:
-        raise SystemExit("    --k must be in 1..64.")
-    if not 0.0 <= args.pimin < 0.5:
-        raise SystemExit("    --pimin must be in [0, 0.5).")
+    _check_k_pimin(args)
     if not 0.0 < args.alpha <= 1.0:
         raise SystemExit("    --alpha must be in (0, 1].")
-    name = os.path.basename(args.data_path)
-    if ".vcf" in name:
-        raise SystemExit("    hwe needs the SNP IDs of a .bim file: it is not available for VCF input.")
-    if ".bed" not in name:
-        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed.")
-    P_path = find_P_files(args.save_dir, args.name, [args.k], what="hwe")[0]       # before anything is read
-    Q_path = relate.find_Q_files(args.save_dir, args.name, [args.k], what="hwe")[0]
-    n, m, bim = _bed_shape(args.data_path)                  # before the GPU check and before any genotype is read
-    ids, _ = ld.read_bim(bim)
-    if len(ids) != m:
-        raise SystemExit(f"    {bim} lists {len(ids)} SNPs, the .bed holds {m}.")
+    _need_bed(args.data_path, "hwe needs the SNP IDs of a .bim file")
+    P_path = find_run_files(args.save_dir, args.name, [args.k], "P", "hwe")[0]     # before anything is read
+    Q_path = find_run_files(args.save_dir, args.name, [args.k], "Q", "hwe")[0]
+    n, _, _, ids, _ = _bed_ids(args.data_path)              # before the GPU check and before any genotype is read
     keep = _extract_keep(args.data_path, args.extract)     # (the .P then has one row per listed SNP)
     if keep is not None:
         ids = [s for s, k in zip(ids, keep) if k]
-    Q = relate.read_matrix_file(Q_path, args.k, n)
-    P = read_P_files([P_path], [args.k], len(ids))[0]
-    if not torch.cuda.is_available():
-        raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
-    torch.set_num_threads(max(1, args.threads))
-    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
+    Q = read_run_matrix(Q_path, args.k, n)
+    P = read_run_matrix(P_path, args.k, len(ids), "model")
+    data = _read_on_gpu(args, keep)
     res = hwe.snp_hwe(data.packed, data.M, P, Q, pimin=args.pimin)
     kept = hwe.hwe_keep(res.p, args.alpha, res.n)
     out = args.out_name or args.name
     os.makedirs(args.save_dir, exist_ok=True)
     hwe.write_table(os.path.join(args.save_dir, f"{out}.{args.k}.hwe"), ids, res)
-    ld.write_id_list(os.path.join(args.save_dir, f"{out}.{args.k}.hwe.in"), [s for s, k in zip(ids, kept) if k])
-    ld.write_id_list(os.path.join(args.save_dir, f"{out}.{args.k}.hwe.out"), [s for s, k in zip(ids, kept) if not k])
+    _write_id_lists(os.path.join(args.save_dir, f"{out}.{args.k}.hwe"), ids, kept)
     Z = res.Z.cpu().numpy()
     Z = Z[~np.isnan(Z)]
     med, sd = (float(np.median(Z)), float(np.std(Z))) if len(Z) else (float("nan"), float("nan"))
@@ -276,42 +289,27 @@ def _kinship_main(argv, t0):
     """``kinship`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.kin (``i j phi n`` per related pair, 0-based
     sample indices, by i then j) and {out_name}.{k}.inbreed (one inbreeding coefficient per sample)."""
     from . import relate
-    from .project import find_P_files, read_P_files
     from .io import savetxt
     args = parse_kinship_args(argv)
-    if args.k < 1 or args.k > 64:
-        raise SystemExit("    --k must be in 1..64.")
-    if not 0.0 <= args.pimin < 0.5:
-        raise SystemExit("    --pimin must be in [0, 0.5).")
+    _check_k_pimin(args)
     if not args.min_phi == args.min_phi:
         raise SystemExit("    --min_phi must be a number.")
     name = os.path.basename(args.data_path)
     if ".bed" not in name and ".vcf" not in name:
         raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
-    P_path = find_P_files(args.save_dir, args.name, [args.k], what="kinship")[0]   # before anything is read
-    Q_path = relate.find_Q_files(args.save_dir, args.name, [args.k])[0]
+    P_path = find_run_files(args.save_dir, args.name, [args.k], "P", "kinship")[0]  # before anything is read
+    Q_path = find_run_files(args.save_dir, args.name, [args.k], "Q", "kinship")[0]
     keep = _extract_keep(args.data_path, args.extract)     # (the .P then has one row per listed SNP)
     n_known = m_known = None
     if ".bed" in name:                                      # the .fam file and the size of the .bed give N and M without reading a genotype
-        from pathlib import Path
-        fam, bed = Path(args.data_path).with_suffix(".fam"), Path(args.data_path).with_suffix(".bed")
-        for f in (fam, bed):
-            if not f.is_file():
-                raise SystemExit(f"    {f} not found.")
-        with open(fam) as fb:
-            n_known = sum(1 for _ in fb)
-        nb = (n_known + 3) // 4
-        if n_known < 1 or (bed.stat().st_size - 3) < nb or (bed.stat().st_size - 3) % nb:
-            raise SystemExit(f"    {bed} does not hold whole SNPs of the {n_known} samples of {fam}.")
-        m_known = (bed.stat().st_size - 3) // nb if keep is None else int(keep.sum())
+        n_known, m_known, _ = _bed_shape(args.data_path, need_bim=False)
+        if keep is not None:
+            m_known = int(keep.sum())
     # both files are read and checked before the genotypes: the widths always, the row counts where the input tells N and M up front
     # (.bed); a VCF's are known only once it is parsed, and are checked then
-    Q = relate.read_matrix_file(Q_path, args.k, n_known)
-    P = read_P_files([P_path], [args.k], m_known)[0] if m_known is not None else relate.read_matrix_file(P_path, args.k, None)
-    if not torch.cuda.is_available():
-        raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
-    torch.set_num_threads(max(1, args.threads))
-    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
+    Q = read_run_matrix(Q_path, args.k, n_known)
+    P = read_run_matrix(P_path, args.k, m_known, "model" if m_known is not None else "data")
+    data = _read_on_gpu(args, keep)
     for path, a, rows in ((Q_path, Q, data.N), (P_path, P, data.M)):
         if a.shape[0] != rows:
             raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the data needs {rows} x {args.k}.")
@@ -385,19 +383,17 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
         torch.distributed.destroy_process_group()
 
 
+_ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main}
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe"), \
         'Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions).'
     mode, t0 = argv[0], time.time()
-    if mode == "kinship":                                   # (its argument and file checks come before the GPU check)
-        return _kinship_main(argv[1:], t0)
-    if mode == "prune":                                     # (likewise)
-        return _prune_main(argv[1:], t0)
-    if mode == "hwe":                                       # (likewise)
-        return _hwe_main(argv[1:], t0)
-    if not torch.cuda.is_available():
-        raise SystemExit("neural_admixture_amd needs a ROCm GPU; use the reference for --num_gpus 0 (CPU) runs.")
+    if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
+        return _ANALYSIS_MODES[mode](argv[1:], t0)
+    _need_gpu()
     if mode == "train":
         args = parse_train_args(argv[1:])
         assert args.epochs > 0 and args.batch_size > 0 and args.learning_rate > 0 and args.hidden_size > 0 and args.n_components > 0
@@ -445,11 +441,10 @@ def main(argv=None):
         cfg = json.load(fb)
     Ps = None
     if args.refine > 0:                                    # the training run's {name}.{k}.P, looked for before anything is loaded
-        from .project import find_P_files, read_P_files
-        P_paths = find_P_files(args.save_dir, args.name, cfg["ks"])
+        P_paths = find_run_files(args.save_dir, args.name, cfg["ks"], "P", "--refine")
     sd = torch.load(f"{args.save_dir}/{args.name}.pt", map_location="cpu", weights_only=True)
     if args.refine > 0:                                    # one row per SNP of the model: V is [M, num_features]
-        Ps = read_P_files(P_paths, cfg["ks"], int(sd["V"].shape[0]))
+        Ps = [read_run_matrix(p, k, int(sd["V"].shape[0]), "model") for p, k in zip(P_paths, cfg["ks"])]
     model = Q_P(int(cfg["hidden_size"]), int(cfg["num_features"]), ks_list=cfg["ks"], is_train=False)
     if args.precision != "highest":
         log.info(f"    Matmul precision: {args.precision} (bf16-class products in the genotype passes).")
@@ -463,8 +458,7 @@ def main(argv=None):
         for h, P_MK in enumerate(Ps):
             eng.load_P(h, P_MK)
         ll0 = ll1 = 0.0
-    for s in range(0, data.N, args.batch_size):
-        bb = min(args.batch_size, data.N - s)
+    for s, bb in row_ranges(data.N, args.batch_size):     # engine.final_q's ranges, with the projection of a batch in between
         qs = eng.infer_q(idx[s:s + bb], bb)
         if Ps is not None:                                 # projection: the encoder's Q is the start of the masked EM steps
             _, lls, _ = eng.project_q(idx[s:s + bb], bb, q0=qs, iters=0, with_loglik=True)

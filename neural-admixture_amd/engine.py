@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, check, ptr, PlanDesc, MODE_SINGLE, MODE_DP, MODE_SNP, PRECISION_HIGHEST, PRECISION_MEDIUM, T_NAMES, MAX_BUCKETS, LABEL_NONE
+from ._packed import pad_Q, stream as _stream
 from .layout import ModelLayout
 
 _f32 = torch.float32
@@ -38,8 +39,17 @@ _PIN_BYTES = 256 << 20                                   # the two pinned stagin
                                                          # 0.40 s per 100k rows; 256-row chunks 0.48, the packing alone 0.34 -- profiles/r05_io_timing.txt)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def row_ranges(n: int, b: int):
+    """``(start, count)`` of the consecutive ranges of at most ``b`` rows that cover the rows 0..n."""
+    return [(s, min(b, n - s)) for s in range(0, n, b)]
+
+
+def final_q(eng, n: int, b: int) -> List[torch.Tensor]:
+    """The encoder's Q of the rows 0..n of ``eng``'s resident matrix, per head ``[n, k]``: ``eng.infer_q`` on ``row_ranges(n, b)``,
+    one after the other.  (A function, not a method: any object with ``device`` and ``infer_q`` will do.)"""
+    seq = torch.arange(n, dtype=torch.int32, device=eng.device)
+    parts = [eng.infer_q(seq[s:s + bb], bb) for s, bb in row_ranges(n, b)]
+    return [torch.cat(q, dim=0) for q in zip(*parts)]
 
 
 class Engine:
@@ -528,6 +538,17 @@ class Engine:
         self.pflat[L.off_v + L.p_off[h]: L.off_v + L.p_off[h] + L.M * L.kp[h]].view(L.M, L.kp[h])[:, : L.ks[h]].copy_(Pt.to(self.device))
         self.invalidate_q()                              # (P was edited: the loss path clamps until the next restrict_P)
 
+    def _analysis(self, what: str, advice: str, resident: bool = True, head: Optional[int] = None) -> None:
+        """The refusals the analysis methods below share: a sharded engine (``advice``: what to do instead), no plan or -- where the
+        method reads it whole (``resident``) -- no packed matrix, a ``head`` the model does not have."""
+        if self.mode != "single" or self.world != 1:
+            raise NotImplementedError(f"Engine.{what} is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
+                                      f"P; {advice} instead")
+        if self._plan is None or (resident and self.xp is None):
+            raise RuntimeError(f"Engine.{what} needs the HIP engine{' with its packed matrix resident' if resident else ''} (no CPU fallback)")
+        if head is not None and not 0 <= head < len(self.lay.ks):
+            raise RuntimeError(f"Engine.{what}: head must be in 0..{len(self.lay.ks) - 1}")
+
     def project_q(self, idx: torch.Tensor, b: int, q0: Optional[Sequence[torch.Tensor]] = None, iters: int = 20, tol: float = 1e-4,
                   with_loglik: bool = False):
         """Per head the [b, k] ancestry fractions of the batch rows idx after ``iters`` masked EM steps against the engine's P held
@@ -537,11 +558,7 @@ class Engine:
         returned Q (float64 [b]) and the number of observed calls (int32 [b]) -> (Qs, lls, nobs).  The number of steps the call ran
         is left in ``self.project_iters`` (0 before the first call; below ``iters`` when the early stop triggered)."""
         from . import project
-        if self.mode != "single" or self.world != 1:
-            raise NotImplementedError("Engine.project_q is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
-                                      "P; project with project.project_q on one GPU from the written .P file instead")
-        if self._plan is None:
-            raise RuntimeError("Engine.project_q needs the HIP engine (no CPU fallback)")
+        self._analysis("project_q", "project with project.project_q on one GPU from the written .P file", resident=False)
         L = self.lay
         if q0 is None:
             q0 = self.infer_q(idx, b)
@@ -549,7 +566,7 @@ class Engine:
             raise RuntimeError("q0 must hold one [b, k] matrix per head")
         big = self.big                                   # (settles what the last step left to the next one)
         Pps = [big[L.p_off[h]: L.p_off[h] + L.M * L.kp[h]].view(L.M, L.kp[h]) for h in range(len(L.ks))]
-        q0p = [project.pad_Q(q, b, k, L.kp[h], self.device) for h, (q, k) in enumerate(zip(q0, L.ks))]
+        q0p = [pad_Q(q, b, k, L.kp[h], self.device) for h, (q, k) in enumerate(zip(q0, L.ks))]
         Qs, lls, nobs, self.project_iters = project.refine_heads(self.xp, L.M, idx, b, Pps, L.ks, q0p, iters, tol, with_loglik=with_loglik)
         Qs = [q[:, :k].clone() for q, k in zip(Qs, L.ks)]
         return (Qs, lls, nobs) if with_loglik else Qs
@@ -560,20 +577,8 @@ class Engine:
         nothing moves by ``tol``).  Returns ``(Ps [M, k], Qs [N, k], ll_before, ll_after, rounds_run)``; the engine's parameters and
         optimiser state are left as they are (the encoder was trained against its own P)."""
         from . import project
-        if self.mode != "single" or self.world != 1:
-            raise NotImplementedError("Engine.polish is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
-                                      "P; polish with project.polish on one GPU from the written .P and .Q files instead")
-        if self._plan is None or self.xp is None:
-            raise RuntimeError("Engine.polish needs the HIP engine with its packed matrix resident (no CPU fallback)")
-        L = self.lay
-        N = int(self.xp.shape[0])
-        seq = torch.arange(N, dtype=torch.int32, device=self.device)
-        Qs = [[] for _ in L.ks]
-        for s in range(0, N, self.bmax):
-            bb = min(self.bmax, N - s)
-            for h, q in enumerate(self.infer_q(seq[s:s + bb], bb)):
-                Qs[h].append(q)
-        return project.polish(self.xp, L.M, [self.P(h) for h in range(len(L.ks))], [torch.cat(q, dim=0) for q in Qs], rounds, tol)
+        self._analysis("polish", "polish with project.polish on one GPU from the written .P and .Q files")
+        return project.polish(self.xp, self.M, [self.P(h) for h in range(len(self.lay.ks))], final_q(self, int(self.xp.shape[0]), self.bmax), rounds, tol)
 
     def kinship(self, head: int = 0, min_phi: Optional[float] = None, pimin: float = 0.0):
         """Admixture-aware kinship (REAP) of the resident matrix's samples from head ``head``'s P and the encoder's final Q
@@ -581,18 +586,9 @@ class Engine:
         (default: the lower edge of third-degree relatives) and every sample's inbreeding coefficient.  A check of the model's
         assumption that the samples are unrelated; the engine's parameters and optimiser state are left as they are."""
         from . import relate
-        if self.mode != "single" or self.world != 1:
-            raise NotImplementedError("Engine.kinship is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
-                                      "P; use relate.kinship_pairs on one GPU from the written .P and .Q files instead")
-        if self._plan is None or self.xp is None:
-            raise RuntimeError("Engine.kinship needs the HIP engine with its packed matrix resident (no CPU fallback)")
-        L = self.lay
-        if not 0 <= head < len(L.ks):
-            raise RuntimeError(f"Engine.kinship: head must be in 0..{len(L.ks) - 1}")
-        N = int(self.xp.shape[0])
-        seq = torch.arange(N, dtype=torch.int32, device=self.device)
-        Q = torch.cat([self.infer_q(seq[s:s + self.bmax], min(self.bmax, N - s))[head] for s in range(0, N, self.bmax)], dim=0)
-        return relate.kinship_pairs(self.xp, L.M, self.P(head), Q, relate.MIN_PHI if min_phi is None else min_phi, pimin=pimin)
+        self._analysis("kinship", "use relate.kinship_pairs on one GPU from the written .P and .Q files", head=head)
+        return relate.kinship_pairs(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], relate.MIN_PHI if min_phi is None else min_phi,
+                                    pimin=pimin)
 
     def snp_hwe(self, head: int = 0, pimin: float = 0.0):
         """Hardy-Weinberg proportions given ancestry, per SNP of the resident matrix, from head ``head``'s P and the encoder's final
@@ -600,18 +596,8 @@ class Engine:
         ``Hexp`` (float64) ``[M]``.  A check of the likelihood the model assumes; the engine's parameters and optimiser state are
         left as they are."""
         from . import hwe
-        if self.mode != "single" or self.world != 1:
-            raise NotImplementedError("Engine.snp_hwe is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
-                                      "P; use hwe.snp_hwe on one GPU from the written .P and .Q files instead")
-        if self._plan is None or self.xp is None:
-            raise RuntimeError("Engine.snp_hwe needs the HIP engine with its packed matrix resident (no CPU fallback)")
-        L = self.lay
-        if not 0 <= head < len(L.ks):
-            raise RuntimeError(f"Engine.snp_hwe: head must be in 0..{len(L.ks) - 1}")
-        N = int(self.xp.shape[0])
-        seq = torch.arange(N, dtype=torch.int32, device=self.device)
-        Q = torch.cat([self.infer_q(seq[s:s + self.bmax], min(self.bmax, N - s))[head] for s in range(0, N, self.bmax)], dim=0)
-        return hwe.snp_hwe(self.xp, L.M, self.P(head), Q, pimin=pimin)
+        self._analysis("snp_hwe", "use hwe.snp_hwe on one GPU from the written .P and .Q files", head=head)
+        return hwe.snp_hwe(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], pimin=pimin)
 
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, check, ptr
-from .project import pad_P, pad_Q, _check_packed, _stream
+from ._packed import model_operands, stream
 
 EPS = 1e-6           # clip of pi and of 1 - pi: the projection's (project.EPS)
 ALPHA = 1e-6         # plink's customary --hwe threshold
@@ -48,16 +48,8 @@ def snp_hwe_sums(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor] = N
     """One ``nadm_snp_hwe`` call on the current stream for the rows ``idx`` (int32, default: every row) of the packed device matrix
     ``xp [rows, ld]``, the allele frequencies ``P [M, K]`` and the ancestry fractions ``Q [b, K]`` (host or device; row s of Q belongs
     to ``idx[s]``).  Returns ``(U, Hexp, n, Hobs)`` on xp's device: float64, float64, int32, int32 ``[M]``."""
-    b = int(idx.numel()) if idx is not None else int(xp.shape[0])
-    _check_packed(xp, idx, b)
-    if idx is not None and (idx.device != xp.device or idx.dim() != 1 or not idx.is_contiguous()):
-        raise RuntimeError("snp_hwe: idx must be a contiguous int32 vector on the packed matrix's device")
     M = int(M)
-    Pp = pad_P(P, xp.device)
-    if Pp.shape[0] != M:
-        raise RuntimeError(f"P has {Pp.shape[0]} rows, the genotypes {M} SNPs")
-    K = int(np.shape(P)[1])
-    Qp = pad_Q(Q, b, K, Pp.shape[1], xp.device)
+    b, K, Pp, Qp = model_operands(xp, M, idx, P, Q, what="snp_hwe")
     n_scr = int(lib.nadm_snp_hwe_scratch_floats(b, M))
     if n_scr <= 0:
         raise RuntimeError(f"snp_hwe: a block of {b} rows over {M} SNPs is not supported")
@@ -68,7 +60,7 @@ def snp_hwe_sums(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor] = N
     n = torch.empty(M, dtype=torch.int32, device=dev)
     Hobs = torch.empty(M, dtype=torch.int32, device=dev)
     check(lib.nadm_snp_hwe(ptr(xp), xp.shape[1], ptr(idx), b, M, ptr(Qp), Qp.stride(0), K, Pp.shape[1], ptr(Pp), float(eps), float(pimin),
-                           ptr(U), ptr(Hexp), ptr(n), ptr(Hobs), ptr(scratch), _stream()), "snp_hwe")
+                           ptr(U), ptr(Hexp), ptr(n), ptr(Hobs), ptr(scratch), stream()), "snp_hwe")
     return U, Hexp, n, Hobs
 
 

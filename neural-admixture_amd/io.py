@@ -1,4 +1,6 @@
-"""Output writers in the reference's formats (src/utils.py:36-67, src/main.py:38-44)."""
+"""Output writers in the reference's formats (src/utils.py:36-67, src/main.py:38-44), the genotype readers, and the readers of what
+the analysis modes take from a run: its ``.P`` / ``.Q`` files, the ``.bim`` and lists of SNP IDs."""
+import os
 from pathlib import Path
 
 from typing import Optional
@@ -213,3 +215,86 @@ def read_vcf_packed(path: str, device: Optional[torch.device] = None, keep_on_de
     if keep_on_device and device is not None and device.type == "cuda":
         out = out.to(device)
     return PackedGenotypes(out, N, M, False)
+
+
+# ---- a run's .P / .Q files ----------------------------------------------------------------------------------------------------
+_RUN_FILES = {"P": "allele frequencies", "Q": "ancestry fractions"}
+
+
+def find_run_files(save_dir: str, name: str, ks, ext: str, what: str) -> list:
+    """The paths ``{save_dir}/{name}.{k}.{ext}`` (``ext``: "P" or "Q") for every k; a missing file ends the run, naming it (``what``:
+    who asks)."""
+    paths = [os.path.join(save_dir, f"{name}.{k}.{ext}") for k in ks]
+    for p in paths:
+        if not os.path.isfile(p):
+            raise SystemExit(f"    {what} needs the {_RUN_FILES[ext]} the training run wrote: {p} not found.")
+    return paths
+
+
+def read_run_matrix(path: str, k: int, rows: Optional[int] = None, needs: str = "data") -> np.ndarray:
+    """A ``.Q`` or ``.P`` file -> float32 [rows, k]; another width, or a row count other than ``rows`` (when given), ends the run,
+    naming the file and who sets the shape (``needs``): the "data" -- its number of samples for a ``.Q``, of SNPs for a ``.P`` -- or
+    the "model" (the rows of the checkpoint's V: the config's ``num_features`` is the width of the encoder's input, not M)."""
+    a = np.loadtxt(path, dtype=np.float32, ndmin=2)
+    if a.shape[1] != int(k) or (rows is not None and a.shape[0] != int(rows)):
+        want = f"{int(rows)} x {int(k)}" if rows is not None else f"one row of {int(k)} columns per sample or SNP"
+        raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the {needs} needs {want}.")
+    return a
+
+
+# ---- SNP ID lists and the .bim file -------------------------------------------------------------------------------------------
+def read_bim(path) -> tuple:
+    """A PLINK ``.bim`` -> ``(ids, chrom_labels)``: column 2 and column 1 of every line, in file order."""
+    ids, chroms = [], []
+    with open(path) as fb:
+        for ln, line in enumerate(fb, 1):
+            f = line.split()
+            if len(f) < 2:
+                raise SystemExit(f"    {path}: line {ln} has fewer than two columns.")
+            chroms.append(f[0])
+            ids.append(f[1])
+    return ids, chroms
+
+
+def chrom_codes(chroms) -> np.ndarray:
+    """Chromosome labels -> int32 codes, equal labels equal codes (numbered by first appearance)."""
+    seen = {}
+    return np.asarray([seen.setdefault(c, len(seen)) for c in chroms], dtype=np.int32)
+
+
+def read_id_list(path) -> list:
+    """A list of SNP IDs, one per line (what ``plink --extract`` reads): the first field of every non-empty line, in file order."""
+    out = []
+    with open(path) as fb:
+        for line in fb:
+            f = line.split()
+            if f:
+                out.append(f[0])
+    return out
+
+
+def write_id_list(path, ids) -> None:
+    with open(path, "w") as fb:
+        for s in ids:
+            fb.write(f"{s}\n")
+
+
+def resolve_ids(bim_ids, wanted, bim_path="the .bim", list_path="the list") -> np.ndarray:
+    """bool ``[M]``: the SNPs of the ``.bim`` whose ID is in ``wanted``.  An ID the ``.bim`` does not hold, or a listed ID that the
+    ``.bim`` holds more than once, ends the run, naming it."""
+    pos, dup = {}, set()
+    for i, s in enumerate(bim_ids):
+        if s in pos:
+            dup.add(s)
+        else:
+            pos[s] = i
+    keep = np.zeros(len(bim_ids), dtype=bool)
+    for s in wanted:
+        if s not in pos:
+            raise SystemExit(f"    SNP ID {s} of {list_path} is not in {bim_path}.")
+        if s in dup:
+            raise SystemExit(f"    SNP ID {s} of {list_path} occurs more than once in {bim_path}.")
+        keep[pos[s]] = True
+    if not keep.any():
+        raise SystemExit(f"    {list_path} lists no SNP.")
+    return keep

@@ -18,16 +18,15 @@ import numpy as np
 import torch
 
 from ._lib import lib, check, ptr
-from .project import _check_packed, _stream
+from ._packed import check_packed, n_rows, stream
+from .io import read_bim, chrom_codes, read_id_list, write_id_list, resolve_ids    # noqa: F401  (their callers' old home)
 
 MAX_WINDOW = 1025            # NADM_LD_MAX_WINDOW + 1: a SNP and its next 1024
 
 
 def _rows(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor], what: str) -> int:
-    rows = int(idx.numel()) if idx is not None else int(xp.shape[0])
-    _check_packed(xp, idx, rows)
-    if idx is not None and (idx.device != xp.device or idx.dim() != 1 or not idx.is_contiguous()):
-        raise RuntimeError(f"{what}: idx must be a contiguous int32 vector on the packed matrix's device")
+    rows = n_rows(xp, idx)
+    check_packed(xp, idx, rows, what)
     if int(M) < 1 or int(M) > 4 * int(xp.shape[1]):
         raise RuntimeError(f"{what}: M must be in 1..{4 * int(xp.shape[1])} for rows of {int(xp.shape[1])} bytes")
     return rows
@@ -38,7 +37,7 @@ def snp_counts(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor] = None) -> 
     xp's device with the number of observed calls, their sum and their sum of squares."""
     rows = _rows(xp, M, idx, "snp_counts")
     cnt = torch.empty((int(M), 3), dtype=torch.int32, device=xp.device)
-    check(lib.nadm_snp_counts(ptr(xp), xp.shape[1], ptr(idx), rows, int(M), ptr(cnt), _stream()), "snp_counts")
+    check(lib.nadm_snp_counts(ptr(xp), xp.shape[1], ptr(idx), rows, int(M), ptr(cnt), stream()), "snp_counts")
     return cnt
 
 
@@ -58,7 +57,7 @@ def ld_band(xp: torch.Tensor, M: int, window: int, m0: int = 0, m1: Optional[int
         raise RuntimeError(f"ld_band: need 0 <= m0 < m1 <= M, got m0 = {m0}, m1 = {m1}, M = {int(M)}")
     r2 = torch.empty((m1 - m0, W), dtype=torch.float64, device=xp.device)
     mom = torch.empty((m1 - m0, W, 6), dtype=torch.int32, device=xp.device) if with_moments else None
-    check(lib.nadm_ld_band(ptr(xp), xp.shape[1], ptr(idx), rows, int(M), m0, m1, W, ptr(r2), ptr(mom), _stream()), "ld_band")
+    check(lib.nadm_ld_band(ptr(xp), xp.shape[1], ptr(idx), rows, int(M), m0, m1, W, ptr(r2), ptr(mom), stream()), "ld_band")
     return (r2, mom) if with_moments else r2
 
 
@@ -160,67 +159,9 @@ def select_snps(data, keep):
         ld_out = ModelLayout.row_stride(M_out)
         out = torch.empty((data.N, ld_out), dtype=torch.uint8, device=xp.device)
         check(lib.nadm_select_snps(ptr(xp), xp.shape[1], data.N, ptr(kidx), M_out, int(bool(flip_file) != bool(data.flipped)), ptr(out),
-                                   ld_out, _stream()), "select_snps")
+                                   ld_out, stream()), "select_snps")
         if home.type != "cuda":
             out = out.to(home)
         else:
             torch.cuda.current_stream().synchronize()        # kidx is freed on return
     return PackedGenotypes(out, data.N, M_out, bool(flip_file))
-
-
-# ---- SNP ID lists and the .bim file -------------------------------------------------------------------------------------------
-def read_bim(path) -> tuple:
-    """A PLINK ``.bim`` -> ``(ids, chrom_labels)``: column 2 and column 1 of every line, in file order."""
-    ids, chroms = [], []
-    with open(path) as fb:
-        for ln, line in enumerate(fb, 1):
-            f = line.split()
-            if len(f) < 2:
-                raise SystemExit(f"    {path}: line {ln} has fewer than two columns.")
-            chroms.append(f[0])
-            ids.append(f[1])
-    return ids, chroms
-
-
-def chrom_codes(chroms) -> np.ndarray:
-    """Chromosome labels -> int32 codes, equal labels equal codes (numbered by first appearance)."""
-    seen = {}
-    return np.asarray([seen.setdefault(c, len(seen)) for c in chroms], dtype=np.int32)
-
-
-def read_id_list(path) -> list:
-    """A list of SNP IDs, one per line (what ``plink --extract`` reads): the first field of every non-empty line, in file order."""
-    out = []
-    with open(path) as fb:
-        for line in fb:
-            f = line.split()
-            if f:
-                out.append(f[0])
-    return out
-
-
-def write_id_list(path, ids) -> None:
-    with open(path, "w") as fb:
-        for s in ids:
-            fb.write(f"{s}\n")
-
-
-def resolve_ids(bim_ids, wanted, bim_path="the .bim", list_path="the list") -> np.ndarray:
-    """bool ``[M]``: the SNPs of the ``.bim`` whose ID is in ``wanted``.  An ID the ``.bim`` does not hold, or a listed ID that the
-    ``.bim`` holds more than once, ends the run, naming it."""
-    pos, dup = {}, set()
-    for i, s in enumerate(bim_ids):
-        if s in pos:
-            dup.add(s)
-        else:
-            pos[s] = i
-    keep = np.zeros(len(bim_ids), dtype=bool)
-    for s in wanted:
-        if s not in pos:
-            raise SystemExit(f"    SNP ID {s} of {list_path} is not in {bim_path}.")
-        if s in dup:
-            raise SystemExit(f"    SNP ID {s} of {list_path} occurs more than once in {bim_path}.")
-        keep[pos[s]] = True
-    if not keep.any():
-        raise SystemExit(f"    {list_path} lists no SNP.")
-    return keep

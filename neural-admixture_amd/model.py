@@ -17,7 +17,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .engine import Engine, PRECISIONS
+from .engine import Engine, PRECISIONS, final_q
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(message)s")
 log = logging.getLogger(__name__)
@@ -308,12 +308,7 @@ class NeuralAdmixture:
             torch.set_num_threads(host_threads)
         eng.sync()                                         # what the last step left to "the next step" (engine.Engine.sync)
         # ---- final Q: sequential batches of <=1024, encoder only (:369-383) ----
-        Qloc = [[] for _ in self.ks_list]
-        for s in range(0, n_local, infer_b):
-            bb = min(infer_b, n_local - s)
-            for h, q in enumerate(eng.infer_q(seq[s:s + bb], bb)):
-                Qloc[h].append(q)
-        Qloc = [torch.cat(q, dim=0) for q in Qloc]
+        Qloc = final_q(eng, n_local, infer_b)
         if world > 1:
             import torch.distributed as dist
             Qs = []
@@ -380,13 +375,7 @@ class NeuralAdmixture:
                 self.epoch_losses[epoch] = loss_acc
                 if logged and self.master:                          # the global batch's loss (the reference's master prints its shard's)
                     log.info(f"            Loss in epoch {epoch:3d} on device {dev} is {loss_acc:,.0f}")
-        seq = torch.arange(N, dtype=torch.int32, device=dev)
-        Qloc = [[] for _ in self.ks_list]
-        for s in range(0, N, infer_b):
-            bb = min(infer_b, N - s)
-            for h, q in enumerate(eng.infer_q(seq[s:s + bb], bb)):
-                Qloc[h].append(q)
-        Qs = [torch.cat(q, dim=0) for q in Qloc]                    # replicated: every rank has every row
+        Qs = final_q(eng, N, infer_b)                               # replicated: every rank has every row
         # log-likelihood report (train.py:134-146): every rank sums over its SNPs, one all-reduce of the doubles
         ll = torch.zeros(len(self.ks_list), dtype=torch.float64, device=dev)
         if dev.type == "cuda" and max(self.ks_list) <= 16:

@@ -15,14 +15,13 @@ a duplicate or twin, (1 + f) / 2 for a sample with itself (f: its inbreeding coe
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import numpy as np
 import torch
 
 from ._lib import lib, check, ptr
-from .project import pad_P, pad_Q, _check_packed, _stream
+from ._packed import check_packed, model_operands, n_rows, stream
 
 ROWS = 1024                  # rows per block side of the dense and the pair form
 MIN_PHI = 2.0 ** -4.5        # lower edge of third-degree relatives (0.0442)
@@ -44,8 +43,8 @@ def kinship_block(xp: torch.Tensor, M: int, Pp: torch.Tensor, k: int, idxA: Opti
     (``pad_Q``; row s belongs to ``idx[s]``).  Returns ``(num, den)`` float64 ``[ba, bb]`` and ``n`` int32 ``[ba, bb]``:
     ``phi = num / (4 den)``."""
     ba, bb = int(QA.shape[0]), int(QB.shape[0])
-    _check_packed(xp, idxA, ba)
-    _check_packed(xp, idxB, bb)
+    check_packed(xp, idxA, ba)
+    check_packed(xp, idxB, bb)
     for t in (Pp, QA, QB):
         if t.dtype != torch.float32 or t.dim() != 2 or t.device != xp.device or t.stride(1) != 1:
             raise RuntimeError("kinship_block: P and Q must be float32 matrices on the packed matrix's device")
@@ -60,7 +59,7 @@ def kinship_block(xp: torch.Tensor, M: int, Pp: torch.Tensor, k: int, idxA: Opti
     den = torch.empty((ba, bb), dtype=torch.float64, device=dev)
     n = torch.empty((ba, bb), dtype=torch.int32, device=dev)
     check(lib.nadm_kinship(ptr(xp), xp.shape[1], ptr(idxA), ba, ptr(idxB), bb, M, ptr(Pp), k, Pp.shape[1], ptr(QA), ptr(QB),
-                           QA.stride(0), pimin, ptr(num), ptr(den), ptr(n), ptr(scratch), _stream()), "kinship")
+                           QA.stride(0), pimin, ptr(num), ptr(den), ptr(n), ptr(scratch), stream()), "kinship")
     return num, den, n
 
 
@@ -69,23 +68,26 @@ def _phi(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
     return torch.where(den != 0, num / (4.0 * den), torch.full_like(num, float("nan")))
 
 
-def _setup(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor], rows: int):
-    N = int(idx.numel()) if idx is not None else int(xp.shape[0])
-    _check_packed(xp, idx, N)
+def _blocks(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor], rows: int, pimin: float):
+    """The ``rows`` x ``rows`` blocks of pairs with a <= b, row band by row band: yields ``(a, b, phi [ba, bb] float64, n [ba, bb]
+    int32)`` of the rows a.. against the rows b.., one ``nadm_kinship`` call each."""
+    check_packed(xp, idx, n_rows(xp, idx))                  # (ahead of the range of ``rows``, as the refusals have always come)
     rows = int(rows)
     if rows < 1 or rows > 4096:
         raise RuntimeError("rows must be in 1..4096")
-    Pp = pad_P(P, xp.device)
-    if Pp.shape[0] != M:
-        raise RuntimeError(f"P has {Pp.shape[0]} rows, the genotypes {M} SNPs")
-    K = int(np.shape(P)[1])
-    Qp = pad_Q(Q, N, K, Pp.shape[1], xp.device)
+    N, K, Pp, Qp = model_operands(xp, M, idx, P, Q)
     rows = min(rows, N)
-    return N, K, Pp, Qp, rows, kinship_scratch(rows, rows, M, xp.device)
+    scratch = kinship_scratch(rows, rows, M, xp.device)
 
-
-def _rows_of(idx: Optional[torch.Tensor], s: int, b: int, device) -> torch.Tensor:
-    return idx[s:s + b] if idx is not None else torch.arange(s, s + b, dtype=torch.int32, device=device)
+    def rows_of(s, b):
+        return idx[s:s + b] if idx is not None else torch.arange(s, s + b, dtype=torch.int32, device=xp.device)
+    for a in range(0, N, rows):
+        ba = min(rows, N - a)
+        ia = rows_of(a, ba)
+        for b in range(a, N, rows):
+            bb = min(rows, N - b)
+            num, den, nn = kinship_block(xp, M, Pp, K, ia, Qp[a:a + ba], rows_of(b, bb), Qp[b:b + bb], pimin, scratch)
+            yield a, b, _phi(num, den), nn
 
 
 def kinship(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor] = None, rows: int = ROWS, pimin: float = 0.0):
@@ -94,24 +96,19 @@ def kinship(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor] = None, 
     ``(phi float64 [N, N], n int32 [N, N])`` on xp's device: the blocks of ``rows`` x ``rows`` pairs with ib <= jb are computed,
     the rest mirrored (phi is symmetric bit for bit).  The diagonal holds (1 + f_a) / 2.  ``pimin`` drops the calls whose
     individual-specific frequency is outside [pimin, 1 - pimin]."""
-    N, K, Pp, Qp, rows, scratch = _setup(xp, M, P, Q, idx, rows)
+    N = n_rows(xp, idx)
     phi = torch.empty((N, N), dtype=torch.float64, device=xp.device)
     n = torch.empty((N, N), dtype=torch.int32, device=xp.device)
-    for a in range(0, N, rows):
-        ba = min(rows, N - a)
-        ia = _rows_of(idx, a, ba, xp.device)
-        for b in range(a, N, rows):
-            bb = min(rows, N - b)
-            num, den, nn = kinship_block(xp, M, Pp, K, ia, Qp[a:a + ba], _rows_of(idx, b, bb, xp.device), Qp[b:b + bb], pimin, scratch)
-            ph = _phi(num, den)
-            if a == b:                                       # the upper triangle of a diagonal block is the one that counts
-                ph = torch.triu(ph) + torch.triu(ph, 1).T
-                nn = torch.triu(nn) + torch.triu(nn, 1).T
-            phi[a:a + ba, b:b + bb] = ph
-            n[a:a + ba, b:b + bb] = nn
-            if a != b:
-                phi[b:b + bb, a:a + ba] = ph.T
-                n[b:b + bb, a:a + ba] = nn.T
+    for a, b, ph, nn in _blocks(xp, M, P, Q, idx, rows, pimin):
+        ba, bb = ph.shape
+        if a == b:                                           # the upper triangle of a diagonal block is the one that counts
+            ph = torch.triu(ph) + torch.triu(ph, 1).T
+            nn = torch.triu(nn) + torch.triu(nn, 1).T
+        phi[a:a + ba, b:b + bb] = ph
+        n[a:a + ba, b:b + bb] = nn
+        if a != b:
+            phi[b:b + bb, a:a + ba] = ph.T
+            n[b:b + bb, a:a + ba] = nn.T
     return phi, n
 
 
@@ -120,26 +117,19 @@ def kinship_pairs(xp: torch.Tensor, M: int, P, Q, min_phi: float = MIN_PHI, rows
     """The related pairs: ``(i, j, phi, n, inbreeding)`` with ``i < j`` int64, ``phi`` float64 and ``n`` int32 of every pair with
     ``phi >= min_phi`` (default: the lower edge of third-degree relatives), ordered by i then j, and ``inbreeding`` float64 [N] =
     ``2 phi_aa - 1`` of every sample, all on xp's device.  One ``rows`` x ``rows`` block is held at a time: works at any N."""
-    N, K, Pp, Qp, rows, scratch = _setup(xp, M, P, Q, idx, rows)
-    dev = xp.device
-    inb = torch.empty(N, dtype=torch.float64, device=dev)
+    N = n_rows(xp, idx)
+    inb = torch.empty(N, dtype=torch.float64, device=xp.device)
     out_i, out_j, out_p, out_n = [], [], [], []
-    for a in range(0, N, rows):
-        ba = min(rows, N - a)
-        ia = _rows_of(idx, a, ba, dev)
-        for b in range(a, N, rows):
-            bb = min(rows, N - b)
-            num, den, nn = kinship_block(xp, M, Pp, K, ia, Qp[a:a + ba], _rows_of(idx, b, bb, dev), Qp[b:b + bb], pimin, scratch)
-            ph = _phi(num, den)
-            keep = ph >= min_phi                             # (NaN compares false)
-            if a == b:
-                inb[a:a + ba] = 2.0 * torch.diagonal(ph) - 1.0
-                keep = torch.triu(keep, 1)
-            ii, jj = torch.nonzero(keep, as_tuple=True)      # row-major: by i, then j
-            out_i.append(ii + a)
-            out_j.append(jj + b)
-            out_p.append(ph[ii, jj])
-            out_n.append(nn[ii, jj])
+    for a, b, ph, nn in _blocks(xp, M, P, Q, idx, rows, pimin):
+        keep = ph >= min_phi                                 # (NaN compares false)
+        if a == b:
+            inb[a:a + ph.shape[0]] = 2.0 * torch.diagonal(ph) - 1.0
+            keep = torch.triu(keep, 1)
+        ii, jj = torch.nonzero(keep, as_tuple=True)          # row-major: by i, then j
+        out_i.append(ii + a)
+        out_j.append(jj + b)
+        out_p.append(ph[ii, jj])
+        out_n.append(nn[ii, jj])
     i, j, p, nn = torch.cat(out_i), torch.cat(out_j), torch.cat(out_p), torch.cat(out_n)
     order = torch.argsort(i * N + j)                         # the blocks of one row band come one after the other
     return i[order], j[order], p[order], nn[order], inb
@@ -153,27 +143,6 @@ def band_counts(phi) -> list:
         out.append((label, edge, int(((phi >= edge) & (phi < upper)).sum())))
         upper = edge
     return out
-
-
-def find_Q_files(save_dir: str, name: str, ks, what: str = "kinship"):
-    """The ``.Q`` analogue of ``project.find_P_files``: the paths ``{save_dir}/{name}.{k}.Q`` for every k; a missing file ends the run,
-    naming it."""
-    import os
-    paths = [os.path.join(save_dir, f"{name}.{k}.Q") for k in ks]
-    for p in paths:
-        if not os.path.isfile(p):
-            raise SystemExit(f"    {what} needs the ancestry fractions the training run wrote: {p} not found.")
-    return paths
-
-
-def read_matrix_file(path: str, k: int, rows: Optional[int] = None) -> np.ndarray:
-    """A ``.Q`` or ``.P`` file -> float32 [rows, k]; another width, or a row count other than ``rows`` (when given: the data's number
-    of samples for a ``.Q``, of SNPs for a ``.P``), ends the run, naming the file."""
-    a = np.loadtxt(path, dtype=np.float32, ndmin=2)
-    if a.shape[1] != int(k) or (rows is not None and a.shape[0] != int(rows)):
-        want = f"{int(rows)} x {int(k)}" if rows is not None else f"one row of {int(k)} columns per sample or SNP"
-        raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the data needs {want}.")
-    return a
 
 
 def write_pairs(path, i, j, phi, n) -> None:

@@ -26,6 +26,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hwe_oracle as HO  # noqa: E402
 import ld_oracle as LO  # noqa: E402
+from packed_rows import dev as _dev, packed as _packed  # noqa: E402
 
 ROWS = 200                   # resident rows of the GPU cases
 # (b, M, K, pimin, rows): every b, M, K and pimin of the issue at least once, not their product.  rows: "list" = a permuted gather
@@ -43,11 +44,6 @@ YARD_U_DEEP, YARD_H_DEEP = 1.093e-06, 7.891e-06                      # b = 12000
 TOL_U, TOL_H = MARGIN * YARD_U, MARGIN * YARD_H
 TOL_U_BIG, TOL_H_BIG = MARGIN * YARD_U_BIG, MARGIN * YARD_H_BIG
 TOL_U_DEEP, TOL_H_DEEP = MARGIN * YARD_U_DEEP, MARGIN * YARD_H_DEEP
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------------ shared data
@@ -382,22 +378,6 @@ def test_public_names():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-def _packed(Gm, dirty=False):
-    """Packed rows [N, ld] on the host, ld = ceil(M/4) rounded up to 16; ``dirty``: every bit that holds no SNP set -- the unused
-    fields of the last byte and the bytes behind it."""
-    from neural_admixture_amd._lib import lib, check, ptr
-    N, M = Gm.shape
-    ld = ((M + 3) // 4 + 15) // 16 * 16
-    out = torch.empty((N, ld), dtype=torch.uint8)
-    check(lib.nadm_pack2bit_host(ptr(torch.from_numpy(np.ascontiguousarray(Gm))), ptr(out), N, M, ld), "pack2bit_host")
-    if dirty:
-        a = out.numpy()
-        a[:, (M + 3) // 4:] = 0xFF
-        if M % 4:
-            a[:, M // 4] |= (0xFF << (2 * (M % 4))) & 0xFF
-    return out
-
-
 def _gpu_sums(xp, M, P, Q, rows, kind, pimin):
     """One call through hwe.snp_hwe_sums -> numpy (U, Hexp, n, Hobs); Q [ROWS, K] are the resident rows' fractions."""
     from neural_admixture_amd import hwe

@@ -17,6 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kinship_oracle as KO  # noqa: E402
+from packed_rows import dev as _dev, packed as _packed  # noqa: E402
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 TOL = 2.0 ** -15
@@ -24,11 +25,6 @@ ROWS = 140                   # resident rows of the GPU cases
 # (ba, bb, M, K, pimin): every ba x bb, M, K and pimin of the issue at least once, not their product
 BLOCKS = [(1, 1, 257, 2, 0.0), (16, 16, 1027, 3, 0.0), (15, 17, 3001, 8, 0.05), (70, 130, 257, 9, 0.0), (130, 70, 1027, 16, 0.05),
           (70, 130, 3001, 20, 0.0), (16, 16, 257, 8, 0.05), (15, 17, 1027, 20, 0.05), (130, 70, 3001, 2, 0.0)]
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------------ CPU
@@ -244,22 +240,6 @@ def test_band_counts():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-def _packed(Gm, dirty=False):
-    """Packed rows [N, ld] on the host, ld = ceil(M/4) rounded up to 16 (the last chunk then reaches past the row's end); ``dirty``:
-    every bit that holds no SNP set -- the unused fields of the last byte and the bytes behind it."""
-    from neural_admixture_amd._lib import lib, check, ptr
-    N, M = Gm.shape
-    ld = ((M + 3) // 4 + 15) // 16 * 16
-    out = torch.empty((N, ld), dtype=torch.uint8)
-    check(lib.nadm_pack2bit_host(ptr(torch.from_numpy(np.ascontiguousarray(Gm))), ptr(out), N, M, ld), "pack2bit_host")
-    if dirty:
-        a = out.numpy()
-        a[:, (M + 3) // 4:] = 0xFF
-        if M % 4:
-            a[:, M // 4] |= (0xFF << (2 * (M % 4))) & 0xFF
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def _case(M, K):
     """ROWS resident rows with the planted cases of kinship_oracle.make_edge_case; the tests leave them as they are."""

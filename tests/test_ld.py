@@ -15,6 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ld_oracle as LO  # noqa: E402
+from packed_rows import dev as _dev  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WMAX = 130
@@ -23,11 +24,6 @@ WMAX = 130
 # group of eight b-tiles), M 1027 with them: 512-SNP boundaries; W >= M at M = 5 and (64, 64, 64)
 SHAPES = [(1, 5, 1), (1, 64, 7), (37, 5, 7), (37, 257, 64), (37, 1027, 130), (64, 64, 1), (64, 64, 64), (64, 257, 7),
           (64, 1027, 64), (131, 5, 130), (131, 257, 130), (131, 1027, 7)]
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------------ CPU

@@ -13,15 +13,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import project_oracle as R  # noqa: E402
+from packed_rows import dev as _dev, packed as _packed  # noqa: E402
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 PROJ_CHUNK = 256             # SNPs per chunk of the accumulate kernel (csrc/nadm_project.hip: PROJ_CHUNK); 64-sample tiles
 SHAPES = [(70, 3001, 3), (130, 2050, 8), (70, 1027, 16)]
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------------ CPU
@@ -133,22 +129,6 @@ def test_sharded_engines_refuse_projection():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-def _packed(Gm, dirty=False):
-    """Packed rows [N, ld] on the host, ld = ceil(M/4) rounded up to 16 (the last chunk then reaches past the row's end); ``dirty``:
-    every bit that holds no SNP set -- the unused fields of the last byte and the bytes behind it."""
-    from neural_admixture_amd._lib import lib, check, ptr
-    N, M = Gm.shape
-    ld = ((M + 3) // 4 + 15) // 16 * 16
-    out = torch.empty((N, ld), dtype=torch.uint8)
-    check(lib.nadm_pack2bit_host(ptr(torch.from_numpy(np.ascontiguousarray(Gm))), ptr(out), N, M, ld), "pack2bit_host")
-    if dirty:
-        a = out.numpy()
-        a[:, (M + 3) // 4:] = 0xFF
-        if M % 4:
-            a[:, M // 4] |= (0xFF << (2 * (M % 4))) & 0xFF
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def _case(M, K, edge=True):
     Gm, P, Q = R.make_case(130, M, K, edge=edge)
