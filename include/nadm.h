@@ -687,6 +687,55 @@ int nadm_snp_hwe(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, i
                  float eps, float pimin, double* U, double* Hexp, int32_t* nobs, int32_t* Hobs,
                  float* scratch, void* stream);
 
+/* ---- Cross-validation over held-out CALLS: the fold of a call, the masked copy, the held-out deviance ----------------------------
+ * ADMIXTURE's --cv: hide a random fold of the observed genotype calls, refit on the rest (nadm_project_q / nadm_project_p on the
+ * masked copy, unchanged), score how well the refit predicts the hidden calls by the binomial deviance; the K with the lowest
+ * error per held-out call is the one to take.
+ *
+ * The fold of a call is a fixed function of (seed, matrix row i, SNP j), all arithmetic in uint32, wrapping:
+ *     mix32(x):          x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ *     row_key(seed, i) = mix32( mix32( (uint32)i ^ (uint32)(seed >> 32) ) + (uint32)seed + 0x9E3779B9 )
+ *     fold(seed, i, j) = ( (uint64) mix32( row_key(seed, i) ^ (uint32)j ) * folds ) >> 32                 in 0 .. folds - 1
+ * i is the row's index in the WHOLE matrix: row0 + the row within the call, so that calls over row ranges agree with one call over
+ * all rows.  Both entries refuse row0 < 0, row0 + rows > 2^31, M > 2^31, folds outside 2..NADM_CV_MAX_FOLDS and fold outside
+ * 0..folds-1.  mix32(0, 1, 2, 0xFFFFFFFF) = 0x0, 0x688990C0, 0xD1132181, 0x6768824A; seed 0, 5 folds, row 0, SNPs 0..11:
+ * 3 3 0 2 0 1 4 1 1 4 4 1.
+ *
+ * nadm_cv_mask: xo [rows, ld] = xp [rows, ld] with every call j < M that is observed (code 0, 1 or 2) and whose fold equals `fold`
+ * replaced by code 3 (missing).  Everything else is copied bit for bit: missing calls, the unused fields of a row's last SNP byte,
+ * the bytes from ceil(M/4) to ld.  xo == xp is allowed (in place); any other overlap of the two [rows, ld] ranges is refused.  A
+ * plain vector kernel (16-byte loads and stores, 64 calls per thread), no scratch.  Exact: the same inputs give the same bytes.
+ * xp, xo 16-byte aligned; ld >= ceil(M/4), ld % 16 == 0, ld < 2^32.  The EM entries then run on xo as on any packed matrix.
+ *
+ * nadm_cv_deviance: rows 0..b of xp (the ORIGINAL matrix; no gather list: the fold belongs to the matrix row), Q [b, k] (row s
+ * belongs to row s, row stride q_stride, a multiple of 4, >= kp, pad cols 0) and ONE head P [M, kp] (kp = nadm_pad_k(k), pad cols
+ * 0).  Over the calls with j < M, code g != 3 and fold(seed, row0 + i, j) == fold:
+ *     pi_ij  = sum_k q_ik p_jk                                      (fp32, fused multiply-adds, k in order, as nadm_snp_hwe)
+ *     r = clip(pi, eps, 1 - eps);   u = clip(1 - pi, eps, 1 - eps)  (u from the UNCLIPPED pi, as nadm_project_p)
+ *     d_ij   = -2 [ g ln r + (2 - g) ln u ] - 4 ln 2 [g == 1]       (the binomial deviance: 0 for a perfect prediction)
+ *     dev_j  = sum_i d_ij                       nheld_j = the number of such calls
+ * dev double [M], nheld int32 [M].  eps in [1e-9, 0.5): an impossible call (g = 2 where pi = 0) costs -4 ln eps, finite.  scratch:
+ * nadm_cv_deviance_scratch_floats(b, M) floats (grows with b and with M).  xp, Q, P, scratch 16-byte, dev 8-byte, nheld 4-byte
+ * aligned; ld as above.
+ * The sum runs in log2 units: s_ij = (g log2 r + (2 - g) log2 u) + 2 [g == 1] in fp32 with the hardware's 1-ulp v_log_f32 (a
+ * heterozygote at pi = 1/2 gives exactly 0), and dev_j = 2 ln 2 (0 - sum s) with the factor applied once, in float64.  A missing
+ * call, a call of another fold, a row >= b and a SNP >= M enter both sums as exactly +0.0f / 0 (the result does not depend on the
+ * pad bits of a row's last byte, nor on P at a SNP nobody observes); a SNP without a held-out call gives dev = +0.0, nheld = 0.
+ * The batch's 64-sample tiles are cut into nadm_cv_deviance_slices(b, M) slices of whole tiles (the rule of nadm_snp_hwe_slices;
+ * never more than 4096 samples in one slice): s is an fp32 sum within a slice in sample order, the slices' partials are added in
+ * float64 in slice order; nheld is an integer sum, exact.  The order depends on (b, M) alone and there are no floating-point
+ * atomics: the same inputs give the same bits.  Every refusal of both entries is reported before anything is launched.
+ * Asynchronous on `stream`. */
+#define NADM_CV_MAX_FOLDS 64
+int nadm_cv_mask(const uint8_t* xp, int64_t ld, int64_t rows, int64_t row0, int64_t M,
+                 uint64_t seed, int32_t folds, int32_t fold, uint8_t* xo, void* stream);
+int32_t nadm_cv_deviance_slices(int32_t b, int64_t M);
+int64_t nadm_cv_deviance_scratch_floats(int32_t b, int64_t M);
+int nadm_cv_deviance(const uint8_t* xp, int64_t ld, int32_t b, int64_t row0, int64_t M,
+                     const float* Q, int32_t q_stride, int32_t k, int32_t kp, const float* P, float eps,
+                     uint64_t seed, int32_t folds, int32_t fold,
+                     double* dev, int32_t* nheld, float* scratch, void* stream);
+
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,
  * random_state=seed).fit(X).means_): the EM iterations of that call in float64 on the host (csrc/nadm_gmm.cpp restates the

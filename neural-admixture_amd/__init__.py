@@ -14,7 +14,8 @@ from .project import project_p, polish    # noqa: F401  (P refitted against a fi
 from .relate import kinship, kinship_pairs    # noqa: F401  (admixture-aware kinship of sample pairs from Q and P)
 from .ld import snp_counts, ld_band, prune, select_snps    # noqa: F401  (LD pruning: windowed r^2, the keep-list, the selection)
 from .hwe import snp_hwe, snp_hwe_sums, hwe_keep    # noqa: F401  (Hardy-Weinberg score test given ancestry, per SNP, from Q and P)
+from .cv import cv_error, mask_fold, heldout_deviance    # noqa: F401  (cross-validation error for choosing K, over held-out calls)
 from . import pack2bit            # noqa: F401  (the reference's native module by its own names: pack2bit.cu:144-147)
 
 __all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish", "kinship", "kinship_pairs",
-           "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep"]
+           "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep", "cv_error", "mask_fold", "heldout_deviance"]

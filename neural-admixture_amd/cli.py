@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -78,6 +78,11 @@ def parse_train_args(argv):
                         "Single-GPU, unsupervised runs only.  0 (default): off")
     p.add_argument("--polish_tol", type=float, default=1e-5,
                    help="stop polishing once no entry of Q or P moves by this much in a round")
+    p.add_argument("--cv", type=int, default=0, metavar="FOLDS",
+                   help="after training (and after --polish), the cross-validation error of every K over FOLDS folds of held-out "
+                        "genotype CALLS, refitted from the matrices about to be written and logged as 'CV error (K=k): x' like "
+                        "ADMIXTURE's --cv; the fold draw uses --seed.  Single-GPU, unsupervised runs only.  0 (default): off")
+    _add_cv_refit(p)
     _add_precision(p)
     _add_extract(p)
     return p.parse_args(argv)
@@ -149,6 +154,44 @@ def parse_hwe_args(argv):
     p.add_argument("--threads", type=int, default=1)
     _add_extract(p)
     return p.parse_args(argv)
+
+
+def _add_cv_refit(p):
+    p.add_argument("--cv_rounds", type=int, default=50, metavar="N",
+                   help="round limit of a fold's refit (default 50).  The refit starts from the full-data answer, which has seen the "
+                        "held-out calls: stopped early it leaks, and the error of a K that is too large comes out too low")
+    p.add_argument("--cv_tol", type=float, default=1e-5,
+                   help="stop a fold's refit once no entry of Q or P moves by this much in a round")
+
+
+def parse_cv_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture cv",
+                                description="Cross-validation error for choosing K: held-out genotype calls, from a run's .P and .Q files")
+    p.add_argument("--data_path", required=True, type=str)
+    p.add_argument("--save_dir", required=True, type=str)
+    p.add_argument("--name", required=True, type=str)
+    p.add_argument("--k", type=int)
+    p.add_argument("--min_k", type=int)
+    p.add_argument("--max_k", type=int)
+    p.add_argument("--folds", type=int, default=5, help="folds the observed calls are cut into (default 5, ADMIXTURE's)")
+    _add_cv_refit(p)
+    p.add_argument("--seed", type=int, default=42, help="seed of the fold draw")
+    p.add_argument("--out_name", type=str, default=None, help="name of the written file (default: --name)")
+    p.add_argument("--threads", type=int, default=1)
+    _add_extract(p)
+    return p.parse_args(argv)
+
+
+def _check_cv_refit(folds, args, flag):
+    """The checks `cv` and `train --cv` share: ``folds`` came with ``flag``."""
+    if not 2 <= folds <= 64:
+        raise SystemExit(f"    {flag} must be in 2..64.")
+    if args.cv_rounds < 1:
+        raise SystemExit("    --cv_rounds must be >= 1.")
+    if not args.cv_tol >= 0.0:
+        raise SystemExit("    --cv_tol must be >= 0.")
+    if args.seed < 0:
+        raise SystemExit("    --seed must be >= 0.")
 
 
 def _need_gpu():
@@ -285,6 +328,53 @@ def _hwe_main(argv, t0):
     return 0
 
 
+def _cv_main(argv, t0):
+    """``cv`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> one ``CV error (K=k): x`` line per K
+    in the log and {out_name}.cv (``K cv_error se n_heldout rounds`` per K)."""
+    from . import cv
+    args = parse_cv_args(argv)
+    if args.k is not None and (args.min_k is not None or args.max_k is not None):
+        raise SystemExit("    --k cannot be given together with --min_k / --max_k.")
+    if args.k is not None:
+        ks = [args.k]
+    elif args.min_k is not None and args.max_k is not None:
+        if args.max_k < args.min_k:
+            raise SystemExit("    --max_k must be >= --min_k.")
+        ks = list(range(args.min_k, args.max_k + 1))
+    else:
+        raise SystemExit("    Please provide either --k or both --min_k and --max_k.")
+    if ks[0] < 1 or ks[-1] > 64:
+        raise SystemExit("    --k, --min_k and --max_k must be in 1..64.")
+    _check_cv_refit(args.folds, args, "--folds")
+    name = os.path.basename(args.data_path)
+    if ".bed" not in name and ".vcf" not in name:
+        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
+    P_paths = find_run_files(args.save_dir, args.name, ks, "P", "cv")               # before anything is read
+    Q_paths = find_run_files(args.save_dir, args.name, ks, "Q", "cv")
+    keep = _extract_keep(args.data_path, args.extract)     # (the .P files then have one row per listed SNP)
+    n_known = m_known = None
+    if ".bed" in name:                                      # N and M without reading a genotype, as the kinship mode has them
+        n_known, m_known, _ = _bed_shape(args.data_path, need_bim=False)
+        if keep is not None:
+            m_known = int(keep.sum())
+    Qs = [read_run_matrix(p, k, n_known) for p, k in zip(Q_paths, ks)]
+    Ps = [read_run_matrix(p, k, m_known, "model" if m_known is not None else "data") for p, k in zip(P_paths, ks)]
+    data = _read_on_gpu(args, keep)
+    for paths, mats, rows in ((Q_paths, Qs, data.N), (P_paths, Ps, data.M)):
+        for path, a in zip(paths, mats):
+            if a.shape[0] != rows:
+                raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the data needs {rows} x {a.shape[1]}.")
+    log.info(f"    Cross-validation over held-out calls: {args.folds} folds, at most {args.cv_rounds} refit rounds per fold.")
+    results = cv.cv_error(data.packed, data.M, Ps, Qs, args.folds, args.cv_rounds, args.cv_tol, args.seed)
+    cv.log_results(results, log)
+    out = args.out_name or args.name
+    os.makedirs(args.save_dir, exist_ok=True)
+    cv.write_table(os.path.join(args.save_dir, f"{out}.cv"), results)
+    log.info("    Cross-validation table saved.")
+    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
+    return 0
+
+
 def _kinship_main(argv, t0):
     """``kinship`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.kin (``i j phi n`` per related pair, 0-based
     sample indices, by i then j) and {out_name}.{k}.inbreed (one inbreeding coefficient per sample)."""
@@ -372,7 +462,7 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
                           master, V, pops, args.min_k, args.max_k, args.n_components, parallelism=args.parallelism,
                           host_threads=args.threads, gmm=args.gmm, precision=args.precision,
                           unlabelled=None if pops is None else (args.unlabelled,), supervised_loss_weight=args.supervised_loss_weight,
-                          polish=args.polish, polish_tol=args.polish_tol)
+                          polish=args.polish, polish_tol=args.polish_tol, cv=args.cv, cv_rounds=args.cv_rounds, cv_tol=args.cv_tol)
     if master:
         save_model(model, args.name, args.save_dir)
         write_outputs(Qs, args.name, K, args.min_k, args.max_k, args.save_dir, Ps)
@@ -383,19 +473,26 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
         torch.distributed.destroy_process_group()
 
 
-_ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main}
+_ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe"), \
-        'Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions).'
+    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv"), \
+        'Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions, "cv" helps to choose K).'
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         return _ANALYSIS_MODES[mode](argv[1:], t0)
-    _need_gpu()
     if mode == "train":
         args = parse_train_args(argv[1:])
+        if args.cv != 0:                                    # like an analysis mode's: before the GPU check; in --polish's words
+            _check_cv_refit(args.cv, args, "--cv")
+            if args.num_gpus > 1:
+                raise SystemExit("    --cv is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
+            if args.pops_path:
+                raise SystemExit("    --cv ignores labels: it is not available with --pops_path (supervised runs).")
+    _need_gpu()
+    if mode == "train":
         assert args.epochs > 0 and args.batch_size > 0 and args.learning_rate > 0 and args.hidden_size > 0 and args.n_components > 0
         if args.polish < 0:
             raise SystemExit("    --polish takes a number of rounds >= 0.")

@@ -580,6 +580,16 @@ class Engine:
         self._analysis("polish", "polish with project.polish on one GPU from the written .P and .Q files")
         return project.polish(self.xp, self.M, [self.P(h) for h in range(len(self.lay.ks))], final_q(self, int(self.xp.shape[0]), self.bmax), rounds, tol)
 
+    def cv_error(self, folds: int = 5, rounds: int = 50, tol: float = 1e-5, seed: int = 0):
+        """Cross-validation error of every head over held-out CALLS of the resident matrix (cv.cv_error; include/nadm.h,
+        nadm_cv_mask / nadm_cv_deviance), refitted from the engine's own P heads and the encoder's final Q: one ``CvResult`` per
+        head; the K with the lowest ``error`` is the one to take.  Needs room for one more copy of the packed matrix; the engine's
+        parameters and optimiser state are left as they are."""
+        from . import cv
+        self._analysis("cv_error", "use cv.cv_error on one GPU from the written .P and .Q files")
+        return cv.cv_error(self.xp, self.M, [self.P(h) for h in range(len(self.lay.ks))], final_q(self, int(self.xp.shape[0]), self.bmax),
+                           folds, rounds, tol, seed)
+
     def kinship(self, head: int = 0, min_phi: Optional[float] = None, pimin: float = 0.0):
         """Admixture-aware kinship (REAP) of the resident matrix's samples from head ``head``'s P and the encoder's final Q
         (relate.kinship_pairs; include/nadm.h, nadm_kinship): ``(i, j, phi, n, inbreeding)``, the pairs i < j with phi >= ``min_phi``

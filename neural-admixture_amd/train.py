@@ -222,7 +222,8 @@ def capped_host_threads(limit: int = 4):
 def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
           num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
           n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto", precision: str = "highest",
-          unlabelled=None, supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5):
+          unlabelled=None, supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5, cv: int = 0,
+          cv_rounds: int = 50, cv_tol: float = 1e-5):
     """The reference's boundary function (see the module docstring and _train).  The host thread pools (torch intra-op, BLAS,
     OpenMP) are capped at ``host_threads`` while it runs -- the reference's CLI does that with --threads (entry.py:138-146), and
     this package's CLI passes its --threads here; the epoch loop itself always runs with torch's pool at 1 (model.py).
@@ -237,23 +238,35 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
     ``polish`` / ``polish_tol`` (keyword, CLI --polish / --polish_tol): after training, up to ``polish`` rounds of block EM over the
     OBSERVED calls (Engine.polish) started from the trained P and the encoder's Q; the returned ``Ps`` and ``Qs`` are then the
     polished ones -- training reads a missing call as genotype 0, which pulls P down wherever calls are missing -- while the
-    returned model stays as trained.  Single-GPU, unsupervised runs only; 0 (the default) calls nothing."""
+    returned model stays as trained.  Single-GPU, unsupervised runs only; 0 (the default) calls nothing.
+    ``cv`` / ``cv_rounds`` / ``cv_tol`` (keyword, CLI --cv / --cv_rounds / --cv_tol): after training -- and after polishing, where
+    ``polish`` is given -- the cross-validation error of every K over ``cv`` folds of held-out CALLS (cv.cv_error, fold seed
+    ``seed``), refitted from the matrices about to be returned, is logged as ``CV error (K=k): x``.  Single-GPU, unsupervised runs
+    only; 0 (the default) calls nothing."""
     if precision not in PRECISIONS:
         raise ValueError("precision must be 'highest' or 'medium'")
     if polish < 0:
         raise ValueError("polish must be >= 0 rounds")
     if polish > 0 and (num_gpus > 1 or pops is not None):
         raise ValueError("polish needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
+    if cv != 0 and not 2 <= cv <= 64:
+        raise ValueError("cv must be 0 or a number of folds in 2..64")
+    if cv > 0 and cv_rounds < 1:
+        raise ValueError("cv_rounds must be >= 1")
+    if cv > 0 and (num_gpus > 1 or pops is not None):
+        raise ValueError("cv needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
     with capped_host_threads(max(1, int(host_threads))):
         return _train(epochs, batch_size, learning_rate, K, seed, data, device, num_gpus, hidden_size, master, V, pops, min_k, max_k,
                       n_components, parallelism=parallelism, gmm=gmm, precision=precision, unlabelled=unlabelled,
-                      supervised_loss_weight=supervised_loss_weight, polish=polish, polish_tol=polish_tol)
+                      supervised_loss_weight=supervised_loss_weight, polish=polish, polish_tol=polish_tol, cv=cv, cv_rounds=cv_rounds,
+                      cv_tol=cv_tol)
 
 
 def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
            num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
            n_components: int = None, *, parallelism: str = "dp", gmm: str = "auto", precision: str = "highest", unlabelled=None,
-           supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5):
+           supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5, cv: int = 0, cv_rounds: int = 50,
+           cv_tol: float = 1e-5):
     """See module docstring.  ``data`` uint8 [N,M] CPU tensor (or an ``io.PackedGenotypes``, e.g. from
     ``io.read_bed_packed``); ``V`` numpy [C,M] (RSVD output,
     svd.py:83); returns Ps (list of [M,k] float32), Qs (list of [N,k] float32), model.
@@ -321,6 +334,10 @@ def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int
         log.info(f"    Log-likelihood of the observed calls before polishing: {ll0:.3f}")
         log.info(f"    Log-likelihood of the observed calls after polishing:  {ll1:.3f}")
         log.info(f"    Polishing rounds run: {ran}")
+        log.info("")
+    if cv > 0:                                             # on the matrices about to be returned
+        from . import cv as _cv
+        _cv.log_results(_cv.cv_error(model.engine.xp, M, Ps, Qs, cv, cv_rounds, cv_tol, seed), log)
         log.info("")
     if master:
         ks = [K] if K is not None else list(range(min_k, max_k + 1))
