@@ -554,6 +554,34 @@ int nadm_project_q(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b,
                    const float* P, int32_t k, int32_t kp, const float* Qin, float* Qout, int32_t q_stride,
                    float eps, float qmin, double* loglik, int32_t* nobs, float* scratch, void* stream);
 
+/* ---- the weighted step and the bootstrap draw: standard errors for Q by resampling SNPs (ADMIXTURE -B) ----------------------
+ * A bootstrap replicate is the same EM on the weighted likelihood sum_j w_j l_j, w_j = how often SNP j was drawn.  No resampled
+ * matrix is made: nadm_project_q_w is nadm_project_q with one more operand, w: M bytes on the device, 16-byte aligned, no byte at
+ * or beyond M is read.  Same two launches, same scratch (nadm_project_scratch_floats), same refusals before any launch, and a
+ * refusal of w == NULL.  With wf = (float)w_j (exact), per observed j:
+ *     a_k += (1 - p_jk) (wf t0) + p_jk (wf t1)        t1 = g_j / r_j, t0 = (2 - g_j) / (1 - r_j) as above
+ *     n   += w_j                                       (int32, exact: the caller keeps sum_j w_j <= 2^31 - 1)
+ *     ll  += wf [ g_j log r_j + (2 - g_j) log(1 - r_j) ]
+ * and the fold is the unweighted one: q'_k = q_k a_k / (2n), n == 0 returns the row as it came.  w = 1 everywhere gives the bits
+ * of nadm_project_q (Q, ll, n).  A SNP with w_j = 0 enters every sum as exactly +0.0f / 0: the result does not depend on P or on
+ * the call there (finite P).  A 256-SNP chunk whose weights are all zero is skipped and its partials written as +0.0f / 0, the
+ * bits the long way gives.  No floating-point atomics: the same inputs give the same bits.  Qout == Qin is allowed.
+ * nadm_project_p needs no weights: a SNP's weight multiplies num and den alike and cancels, so a replicate's P step is the
+ * unweighted one.
+ *
+ * The bootstrap draw (host side; bootstrap.block_weights restates it in numpy): the M SNPs are cut into nb = ceil(M / block)
+ * blocks of `block` consecutive SNPs (the last may be short); for replicate r, with mix32 and row_key of the cv fold below, all
+ * arithmetic in uint32, wrapping:
+ *     key   = row_key(seed, r)
+ *     c_t   = ( (uint64) mix32( key ^ (uint32)t ) * nb ) >> 32          the block that draw t = 0 .. nb - 1 picks
+ *     cnt_c = #{ t : c_t == c }                 w_j = cnt_{j / block}
+ * Refused: nb < 2, M > 2^31, any cnt > 255 (a weight is a byte).  row_key(0, 0) = 0x01FCE552, row_key(0, 1) = 0xB21C8E52; seed 0,
+ * 12 blocks, replicate 0: the draws pick 8 7 0 5 2 4 11 2 4 10 11 3, so cnt = 1 0 2 1 2 1 0 1 1 0 1 2; replicate 1:
+ * cnt = 2 1 1 0 1 1 2 3 0 0 0 1. */
+int nadm_project_q_w(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                     const float* P, int32_t k, int32_t kp, const float* Qin, float* Qout, int32_t q_stride,
+                     float eps, float qmin, double* loglik, int32_t* nobs, float* scratch, const uint8_t* w, void* stream);
+
 /* ---- the other half: refit P against a FIXED Q with a masked EM step -------------------------------------------------------
  * With nadm_project_q this is the FRAPPE / ADMIXTURE block EM over the OBSERVED calls only.  One call = one step for the rows
  * idx[0..b) (idx == NULL: rows 0..b; any order, a duplicate counts as often as it occurs), Q [b, k] (row s belongs to idx[s],

@@ -15,7 +15,9 @@ from .relate import kinship, kinship_pairs    # noqa: F401  (admixture-aware kin
 from .ld import snp_counts, ld_band, prune, select_snps    # noqa: F401  (LD pruning: windowed r^2, the keep-list, the selection)
 from .hwe import snp_hwe, snp_hwe_sums, hwe_keep    # noqa: F401  (Hardy-Weinberg score test given ancestry, per SNP, from Q and P)
 from .cv import cv_error, mask_fold, heldout_deviance    # noqa: F401  (cross-validation error for choosing K, over held-out calls)
+from .bootstrap import bootstrap_q, block_weights    # noqa: F401  (bootstrap standard errors of Q: SNPs resampled, weighted refits)
 from . import pack2bit            # noqa: F401  (the reference's native module by its own names: pack2bit.cu:144-147)
 
 __all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish", "kinship", "kinship_pairs",
-           "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep", "cv_error", "mask_fold", "heldout_deviance"]
+           "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep", "cv_error", "mask_fold", "heldout_deviance",
+           "bootstrap_q", "block_weights"]

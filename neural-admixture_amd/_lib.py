@@ -104,6 +104,7 @@ def _load():
         "nadm_loglik": (C.c_int, [vp, i64, i64, i64, vp, vp, i32, i32, C.c_double, vp, vp]),
         "nadm_project_scratch_floats": (i64, [i32, i64, i32]),
         "nadm_project_q": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp]),
+        "nadm_project_q_w": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp]),
         "nadm_project_p_slices": (i32, [i32, i64]),
         "nadm_project_p_scratch_floats": (i64, [i32, i64, i32]),
         "nadm_project_p": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp]),

@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv|bootstrap ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -83,6 +83,11 @@ def parse_train_args(argv):
                         "genotype CALLS, refitted from the matrices about to be written and logged as 'CV error (K=k): x' like "
                         "ADMIXTURE's --cv; the fold draw uses --seed.  Single-GPU, unsupervised runs only.  0 (default): off")
     _add_cv_refit(p)
+    p.add_argument("--bootstrap", type=int, default=0, metavar="B",
+                   help="after training (and after --polish), bootstrap standard errors of every K's Q from B replicates that resample "
+                        "the SNPs, refitted from the matrices about to be written: {name}.{K}.Q_se and .Q_bias like ADMIXTURE's -B; "
+                        "the draw uses --seed.  Single-GPU, unsupervised runs only.  0 (default): off")
+    _add_boot_refit(p)
     _add_precision(p)
     _add_extract(p)
     return p.parse_args(argv)
@@ -164,15 +169,44 @@ def _add_cv_refit(p):
                    help="stop a fold's refit once no entry of Q or P moves by this much in a round")
 
 
-def parse_cv_args(argv):
-    p = argparse.ArgumentParser(prog="neural-admixture cv",
-                                description="Cross-validation error for choosing K: held-out genotype calls, from a run's .P and .Q files")
+def _add_boot_refit(p):
+    p.add_argument("--block", type=int, default=1, metavar="SNPS",
+                   help="SNPs are resampled in blocks of this many consecutive SNPs (default 1, ADMIXTURE's per-SNP bootstrap, which "
+                        "takes the SNPs as independent); on data that was not LD-pruned use a block of hundreds of SNPs")
+    p.add_argument("--boot_rounds", type=int, default=50, metavar="N",
+                   help="round limit of a replicate's refit (default 50).  A replicate starts at the estimate: stopped early it has "
+                        "not moved far from it, and the standard error comes out too small")
+    p.add_argument("--boot_tol", type=float, default=1e-5,
+                   help="stop a replicate's refit once no entry of Q or P moves by this much in a round")
+
+
+def _add_run_heads(p):
+    """Where an analysis mode over several K finds a run's files."""
     p.add_argument("--data_path", required=True, type=str)
     p.add_argument("--save_dir", required=True, type=str)
     p.add_argument("--name", required=True, type=str)
     p.add_argument("--k", type=int)
     p.add_argument("--min_k", type=int)
     p.add_argument("--max_k", type=int)
+
+
+def parse_bootstrap_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture bootstrap",
+                                description="Bootstrap standard errors of Q: SNPs resampled with replacement, from a run's .P and .Q files")
+    _add_run_heads(p)
+    p.add_argument("-B", "--replicates", type=int, default=200, help="bootstrap replicates (default 200, ADMIXTURE's)")
+    _add_boot_refit(p)
+    p.add_argument("--seed", type=int, default=42, help="seed of the draw")
+    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
+    p.add_argument("--threads", type=int, default=1)
+    _add_extract(p)
+    return p.parse_args(argv)
+
+
+def parse_cv_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture cv",
+                                description="Cross-validation error for choosing K: held-out genotype calls, from a run's .P and .Q files")
+    _add_run_heads(p)
     p.add_argument("--folds", type=int, default=5, help="folds the observed calls are cut into (default 5, ADMIXTURE's)")
     _add_cv_refit(p)
     p.add_argument("--seed", type=int, default=42, help="seed of the fold draw")
@@ -190,6 +224,20 @@ def _check_cv_refit(folds, args, flag):
         raise SystemExit("    --cv_rounds must be >= 1.")
     if not args.cv_tol >= 0.0:
         raise SystemExit("    --cv_tol must be >= 0.")
+    if args.seed < 0:
+        raise SystemExit("    --seed must be >= 0.")
+
+
+def _check_boot_refit(B, args, flag):
+    """The checks `bootstrap` and `train --bootstrap` share: ``B`` came with ``flag``."""
+    if B < 2:
+        raise SystemExit(f"    {flag} must be >= 2.")
+    if args.block < 1:
+        raise SystemExit("    --block must be >= 1.")
+    if args.boot_rounds < 1:
+        raise SystemExit("    --boot_rounds must be >= 1.")
+    if not args.boot_tol >= 0.0:
+        raise SystemExit("    --boot_tol must be >= 0.")
     if args.seed < 0:
         raise SystemExit("    --seed must be >= 0.")
 
@@ -328,11 +376,8 @@ def _hwe_main(argv, t0):
     return 0
 
 
-def _cv_main(argv, t0):
-    """``cv`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> one ``CV error (K=k): x`` line per K
-    in the log and {out_name}.cv (``K cv_error se n_heldout rounds`` per K)."""
-    from . import cv
-    args = parse_cv_args(argv)
+def _ks_asked(args):
+    """The K list of --k or --min_k .. --max_k."""
     if args.k is not None and (args.min_k is not None or args.max_k is not None):
         raise SystemExit("    --k cannot be given together with --min_k / --max_k.")
     if args.k is not None:
@@ -345,12 +390,17 @@ def _cv_main(argv, t0):
         raise SystemExit("    Please provide either --k or both --min_k and --max_k.")
     if ks[0] < 1 or ks[-1] > 64:
         raise SystemExit("    --k, --min_k and --max_k must be in 1..64.")
-    _check_cv_refit(args.folds, args, "--folds")
+    return ks
+
+
+def _read_run_heads(args, ks, mode):
+    """{save_dir}/{name}.{K}.P and .Q of every K + the genotypes in HBM -> (data, Ps, Qs); every file is looked for and read before
+    the GPU check, and a matrix of the wrong shape ends the run, naming its file."""
     name = os.path.basename(args.data_path)
     if ".bed" not in name and ".vcf" not in name:
         raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
-    P_paths = find_run_files(args.save_dir, args.name, ks, "P", "cv")               # before anything is read
-    Q_paths = find_run_files(args.save_dir, args.name, ks, "Q", "cv")
+    P_paths = find_run_files(args.save_dir, args.name, ks, "P", mode)               # before anything is read
+    Q_paths = find_run_files(args.save_dir, args.name, ks, "Q", mode)
     keep = _extract_keep(args.data_path, args.extract)     # (the .P files then have one row per listed SNP)
     n_known = m_known = None
     if ".bed" in name:                                      # N and M without reading a genotype, as the kinship mode has them
@@ -364,6 +414,17 @@ def _cv_main(argv, t0):
         for path, a in zip(paths, mats):
             if a.shape[0] != rows:
                 raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the data needs {rows} x {a.shape[1]}.")
+    return data, Ps, Qs
+
+
+def _cv_main(argv, t0):
+    """``cv`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> one ``CV error (K=k): x`` line per K
+    in the log and {out_name}.cv (``K cv_error se n_heldout rounds`` per K)."""
+    from . import cv
+    args = parse_cv_args(argv)
+    ks = _ks_asked(args)
+    _check_cv_refit(args.folds, args, "--folds")
+    data, Ps, Qs = _read_run_heads(args, ks, "cv")
     log.info(f"    Cross-validation over held-out calls: {args.folds} folds, at most {args.cv_rounds} refit rounds per fold.")
     results = cv.cv_error(data.packed, data.M, Ps, Qs, args.folds, args.cv_rounds, args.cv_tol, args.seed)
     cv.log_results(results, log)
@@ -371,6 +432,23 @@ def _cv_main(argv, t0):
     os.makedirs(args.save_dir, exist_ok=True)
     cv.write_table(os.path.join(args.save_dir, f"{out}.cv"), results)
     log.info("    Cross-validation table saved.")
+    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
+    return 0
+
+
+def _bootstrap_main(argv, t0):
+    """``bootstrap`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.Q_se and .Q_bias
+    (N x K, the .Q text format) and one ``Bootstrap SE (K=k)`` line per K in the log."""
+    from . import bootstrap
+    args = parse_bootstrap_args(argv)
+    ks = _ks_asked(args)
+    _check_boot_refit(args.replicates, args, "-B / --replicates")
+    data, Ps, Qs = _read_run_heads(args, ks, "bootstrap")
+    log.info(f"    Bootstrap over SNPs: {args.replicates} replicates, blocks of {args.block}, at most {args.boot_rounds} refit rounds each.")
+    results = bootstrap.bootstrap_q(data.packed, data.M, Ps, Qs, args.replicates, args.block, args.boot_rounds, args.boot_tol, args.seed)
+    bootstrap.log_results(results, log, args.boot_rounds)
+    bootstrap.write_results(args.save_dir, args.out_name or args.name, results)
+    log.info("    Standard errors and biases of Q saved.")
     log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
     return 0
 
@@ -462,10 +540,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
                           master, V, pops, args.min_k, args.max_k, args.n_components, parallelism=args.parallelism,
                           host_threads=args.threads, gmm=args.gmm, precision=args.precision,
                           unlabelled=None if pops is None else (args.unlabelled,), supervised_loss_weight=args.supervised_loss_weight,
-                          polish=args.polish, polish_tol=args.polish_tol, cv=args.cv, cv_rounds=args.cv_rounds, cv_tol=args.cv_tol)
+                          polish=args.polish, polish_tol=args.polish_tol, cv=args.cv, cv_rounds=args.cv_rounds, cv_tol=args.cv_tol,
+                          bootstrap=args.bootstrap, boot_block=args.block, boot_rounds=args.boot_rounds, boot_tol=args.boot_tol)
     if master:
         save_model(model, args.name, args.save_dir)
         write_outputs(Qs, args.name, K, args.min_k, args.max_k, args.save_dir, Ps)
+        if args.bootstrap > 0:
+            from .bootstrap import write_results
+            write_results(args.save_dir, args.name, model.boot_results)
         log.info("    Q and P matrices saved." if K is not None else "    Q and P matrices saved for all K.")
         log.info("")
         log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
@@ -473,13 +555,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
         torch.distributed.destroy_process_group()
 
 
-_ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main}
+_ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv"), \
-        'Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions, "cv" helps to choose K).'
+    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv", "bootstrap"), \
+        ('Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions, '
+         '"cv" helps to choose K, "bootstrap" puts standard errors on Q).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         return _ANALYSIS_MODES[mode](argv[1:], t0)
@@ -491,6 +574,12 @@ def main(argv=None):
                 raise SystemExit("    --cv is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
             if args.pops_path:
                 raise SystemExit("    --cv ignores labels: it is not available with --pops_path (supervised runs).")
+        if args.bootstrap != 0:
+            _check_boot_refit(args.bootstrap, args, "--bootstrap")
+            if args.num_gpus > 1:
+                raise SystemExit("    --bootstrap is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
+            if args.pops_path:
+                raise SystemExit("    --bootstrap ignores labels: it is not available with --pops_path (supervised runs).")
     _need_gpu()
     if mode == "train":
         assert args.epochs > 0 and args.batch_size > 0 and args.learning_rate > 0 and args.hidden_size > 0 and args.n_components > 0

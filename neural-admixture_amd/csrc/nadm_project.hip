@@ -6,6 +6,9 @@
 //                         registers; the chunk's P rows sit in LDS once per block and every lane reads the SAME row (a broadcast).
 //                         Missing calls (code 3) and SNPs >= M enter every sum as exactly +0.0f.  Writes the chunk's partials of
 //                         a_k (fp32), n (int32) and, when asked, ll (fp32).
+//                         The WEIGHTED form (nadm_project_q_w, bootstrap replicates) multiplies every SNP's terms by its count w_j:
+//                         the chunk's 256 weight bytes sit in LDS next to the P rows and every lane reads the same byte; a chunk
+//                         whose weights are all zero writes +0.0f / 0 partials and returns (wave-uniform).
 //   project_fold_kernel   one wave per sample: adds the partials over the chunks in a fixed order (a, ll in float64) and applies
 //                         q'_k = q_k a_k / (2n), the floor qmin, the renormalisation.
 #include "nadm_common.h"
@@ -19,11 +22,18 @@ constexpr int PROJ_TILE = 64;        // samples per block (one wave, a lane per 
 // KP <= 16: the whole chunk of P is staged at once (16 KB at KP = 16); wider heads stage 64 SNPs at a time (16 KB at KP = 64)
 template <int KP> struct ProjStage { static constexpr int SNPS = KP <= 16 ? PROJ_CHUNK : 64; };
 
-template <int KP, bool WITH_LL>
+// the chunk's weights in LDS, one byte per SNP (the WEIGHTED instantiations only: the others never name it and get no LDS for it)
+__device__ __forceinline__ uint32_t* proj_weight_lds() {
+    __shared__ __attribute__((aligned(16))) uint32_t Wl[PROJ_CHUNK / 4];
+    return Wl;
+}
+
+template <int KP, bool WITH_LL, bool WEIGHTED>
 __global__ __launch_bounds__(PROJ_TILE) void project_accum_kernel(
     const uint8_t* __restrict__ xp, const int64_t ld, const int32_t* __restrict__ idx, const int b, const int64_t M,
     const float* __restrict__ P, const float* __restrict__ Qin, const int q_stride, const float eps, const float one_m_eps,
-    const int tiles, float* __restrict__ apart, int32_t* __restrict__ npart, float* __restrict__ llpart) {
+    const int tiles, float* __restrict__ apart, int32_t* __restrict__ npart, float* __restrict__ llpart,
+    const uint8_t* __restrict__ wts) {
     constexpr int STAGE = ProjStage<KP>::SNPS;
     __shared__ __attribute__((aligned(16))) float Ps[STAGE * KP];
     const int lane = threadIdx.x;
@@ -32,6 +42,29 @@ __global__ __launch_bounds__(PROJ_TILE) void project_accum_kernel(
     const int s = tile * PROJ_TILE + lane;
     const bool live = s < b;
     const int64_t j0 = chunk * PROJ_CHUNK;
+
+    if constexpr (WEIGHTED) {
+        // lane l brings the weights of SNPs j0 + 4l .. j0 + 4l + 3 (no byte at or beyond M is read; those SNPs are masked anyway)
+        const int64_t jw = j0 + 4 * lane;
+        uint32_t ww = 0u;
+        if (jw + 4 <= M) {
+            ww = *reinterpret_cast<const uint32_t*>(wts + jw);
+        } else {
+            for (int t = 0; t < 4; ++t)
+                if (jw + t < M) ww |= (uint32_t)wts[jw + t] << (8 * t);
+        }
+        if (__ballot(ww != 0u) == 0ull) {                       // nothing of this chunk was drawn: the sums the long way are +0.0f / 0
+            if (live) {
+                const int64_t o = chunk * b + s;
+#pragma unroll
+                for (int k = 0; k < KP; k += 4) *reinterpret_cast<float4*>(apart + o * KP + k) = make_float4(0.f, 0.f, 0.f, 0.f);
+                npart[o] = 0;
+                if constexpr (WITH_LL) llpart[o] = 0.f;
+            }
+            return;
+        }
+        proj_weight_lds()[lane] = ww;                           // visible after the first stage's barrier
+    }
 
     // this lane's row: the chunk's 64 bytes (16-byte pieces past the row's end read as zeros; their SNPs are >= M anyway)
     uint32_t w[16];
@@ -92,13 +125,25 @@ __global__ __launch_bounds__(PROJ_TILE) void project_accum_kernel(
                 float rr = 0.f;
 #pragma unroll
                 for (int k = 0; k < KP; ++k) rr = fmaf(q[k], p[k], rr);
-                const EmTerms e = em_terms(rr, code, m, eps, one_m_eps);
+                EmTerms e = em_terms(rr, code, m, eps, one_m_eps);
+                uint32_t wj = 1u;
+                float wf = 1.f;
+                if constexpr (WEIGHTED) {                        // every lane reads the same byte: a broadcast
+                    wj = reinterpret_cast<const uint8_t*>(proj_weight_lds())[wi * 16 + t];
+                    wf = (float)wj;
+                    e.t1 *= wf;
+                    e.t0 *= wf;
+                }
                 // both terms as they stand: (1 - p_jk) / (1 - r_j) <= 1 / q_k however small 1 - r_j gets, whereas the cheaper
                 // sum_j t0_j + sum_j p_jk (t1_j - t0_j) cancels two sums of ~1/eps when a row of P is all ones
 #pragma unroll
                 for (int k = 0; k < KP; ++k) a[k] = fmaf(1.f - p[k], e.t0, fmaf(p[k], e.t1, a[k]));
-                n += (int)(m & 1u);
-                if constexpr (WITH_LL) llw += keepf(e.g * __log2f(e.r) + e.h * __log2f(e.u), m);      // v_log_f32; ln 2 once per word
+                if constexpr (WEIGHTED) n += (int)(wj & m);
+                else n += (int)(m & 1u);
+                if constexpr (WITH_LL) {                                                               // v_log_f32; ln 2 once per word
+                    if constexpr (WEIGHTED) llw = fmaf(wf, keepf(e.g * __log2f(e.r) + e.h * __log2f(e.u), m), llw);
+                    else llw += keepf(e.g * __log2f(e.r) + e.h * __log2f(e.u), m);
+                }
             }
             if constexpr (WITH_LL) ll += llw * 0.693147180559945f;
         }
@@ -155,16 +200,17 @@ __global__ __launch_bounds__(64) void project_fold_kernel(const float* __restric
     }
 }
 
-template <int KP>
+template <int KP, bool WEIGHTED>
 static void launch_accum(bool with_ll, unsigned grid, hipStream_t st, const uint8_t* xp, int64_t ld, const int32_t* idx, int b, int64_t M,
-                         const float* P, const float* Qin, int q_stride, float eps, int tiles, float* apart, int32_t* npart, float* llpart) {
+                         const float* P, const float* Qin, int q_stride, float eps, int tiles, float* apart, int32_t* npart, float* llpart,
+                         const uint8_t* wts) {
     const float ome = 1.f - eps;
     if (with_ll)
-        hipLaunchKernelGGL((project_accum_kernel<KP, true>), dim3(grid), dim3(PROJ_TILE), 0, st, xp, ld, idx, b, M, P, Qin, q_stride, eps, ome,
-                           tiles, apart, npart, llpart);
+        hipLaunchKernelGGL((project_accum_kernel<KP, true, WEIGHTED>), dim3(grid), dim3(PROJ_TILE), 0, st, xp, ld, idx, b, M, P, Qin, q_stride, eps,
+                           ome, tiles, apart, npart, llpart, wts);
     else
-        hipLaunchKernelGGL((project_accum_kernel<KP, false>), dim3(grid), dim3(PROJ_TILE), 0, st, xp, ld, idx, b, M, P, Qin, q_stride, eps, ome,
-                           tiles, apart, npart, llpart);
+        hipLaunchKernelGGL((project_accum_kernel<KP, false, WEIGHTED>), dim3(grid), dim3(PROJ_TILE), 0, st, xp, ld, idx, b, M, P, Qin, q_stride, eps,
+                           ome, tiles, apart, npart, llpart, wts);
 }
 
 static int64_t project_chunks(int64_t M) { return (M + PROJ_CHUNK - 1) / PROJ_CHUNK; }
@@ -179,30 +225,50 @@ extern "C" int64_t nadm_project_scratch_floats(int32_t b, int64_t M, int32_t kp)
     return project_chunks(M) * (int64_t)b * (kp + 2);
 }
 
-extern "C" int nadm_project_q(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* P, int32_t k, int32_t kp,
-                              const float* Qin, float* Qout, int32_t q_stride, float eps, float qmin, double* loglik, int32_t* nobs,
-                              float* scratch, void* stream) {
-    if (!xp || !P || !Qin || !Qout || !scratch) return fail("nadm_project_q: null pointer");
-    if (b <= 0 || M <= 0) return fail("nadm_project_q: empty batch (need b > 0 and M > 0)");
-    if (check_packed("nadm_project_q", ld, M) || check_head("nadm_project_q", k, kp, q_stride) || check_eps("nadm_project_q", eps)) return 1;
-    if (!(qmin >= 0.f && qmin < 1.f)) return fail("nadm_project_q: qmin must be in [0, 1)");
+// both entries: `who` names the caller in a refusal, wts == NULL runs the unweighted instantiations
+static int project_q_any(const char* who, const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* P, int32_t k,
+                         int32_t kp, const float* Qin, float* Qout, int32_t q_stride, float eps, float qmin, double* loglik, int32_t* nobs,
+                         float* scratch, const uint8_t* wts, bool weighted, void* stream) {
+    if (!xp || !P || !Qin || !Qout || !scratch || (weighted && !wts)) return failf(who, "null pointer");
+    if (b <= 0 || M <= 0) return failf(who, "empty batch (need b > 0 and M > 0)");
+    if (check_packed(who, ld, M) || check_head(who, k, kp, q_stride) || check_eps(who, eps)) return 1;
+    if (!(qmin >= 0.f && qmin < 1.f)) return failf(who, "qmin must be in [0, 1)");
     if ((((uintptr_t)xp | (uintptr_t)P | (uintptr_t)Qin | (uintptr_t)Qout | (uintptr_t)scratch) & 15) != 0)
-        return fail("nadm_project_q: xp, P, Qin, Qout and scratch must be 16-byte aligned");
+        return failf(who, "xp, P, Qin, Qout and scratch must be 16-byte aligned");
+    if (weighted && ((uintptr_t)wts & 15) != 0) return failf(who, "w must be 16-byte aligned");
     const int64_t chunks = project_chunks(M);
     const int tiles = (b + PROJ_TILE - 1) / PROJ_TILE;
-    if (chunks * tiles > 0x7FFFFFFFll) return fail("nadm_project_q: too many (chunk, tile) blocks for one launch");
+    if (chunks * tiles > 0x7FFFFFFFll) return failf(who, "too many (chunk, tile) blocks for one launch");
     float* apart = scratch;
     int32_t* npart = reinterpret_cast<int32_t*>(scratch + chunks * b * kp);
     float* llpart = loglik ? scratch + chunks * b * (kp + 1) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(chunks * tiles);
     const bool wl = loglik != nullptr;
-    if (int e = dispatch_kp("nadm_project_q", kp, [&](auto KP) {
-            launch_accum<decltype(KP)::value>(wl, grid, st, xp, ld, idx, b, M, P, Qin, q_stride, eps, tiles, apart, npart, llpart);
+    if (int e = dispatch_kp(who, kp, [&](auto KP) {
+            if (weighted)
+                launch_accum<decltype(KP)::value, true>(wl, grid, st, xp, ld, idx, b, M, P, Qin, q_stride, eps, tiles, apart, npart, llpart, wts);
+            else
+                launch_accum<decltype(KP)::value, false>(wl, grid, st, xp, ld, idx, b, M, P, Qin, q_stride, eps, tiles, apart, npart, llpart,
+                                                         nullptr);
         }))
         return e;
     if (int e = check_launch("project_q (accumulate)")) return e;
     hipLaunchKernelGGL(project_fold_kernel, dim3((unsigned)b), dim3(64), 0, st, apart, npart, llpart, chunks, b, k, kp, Qin, Qout, q_stride, qmin,
                        loglik, nobs);
     return check_launch("project_q (fold)");
+}
+
+extern "C" int nadm_project_q(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* P, int32_t k, int32_t kp,
+                              const float* Qin, float* Qout, int32_t q_stride, float eps, float qmin, double* loglik, int32_t* nobs,
+                              float* scratch, void* stream) {
+    return project_q_any("nadm_project_q", xp, ld, idx, b, M, P, k, kp, Qin, Qout, q_stride, eps, qmin, loglik, nobs, scratch, nullptr, false,
+                         stream);
+}
+
+extern "C" int nadm_project_q_w(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* P, int32_t k, int32_t kp,
+                                const float* Qin, float* Qout, int32_t q_stride, float eps, float qmin, double* loglik, int32_t* nobs,
+                                float* scratch, const uint8_t* w, void* stream) {
+    return project_q_any("nadm_project_q_w", xp, ld, idx, b, M, P, k, kp, Qin, Qout, q_stride, eps, qmin, loglik, nobs, scratch, w, true,
+                         stream);
 }

@@ -590,6 +590,16 @@ class Engine:
         return cv.cv_error(self.xp, self.M, [self.P(h) for h in range(len(self.lay.ks))], final_q(self, int(self.xp.shape[0]), self.bmax),
                            folds, rounds, tol, seed)
 
+    def bootstrap_q(self, B: int = 200, block: int = 1, rounds: int = 50, tol: float = 1e-5, seed: int = 0):
+        """Bootstrap standard errors of every head's Q on the resident matrix (bootstrap.bootstrap_q; include/nadm.h,
+        nadm_project_q_w): SNPs resampled in blocks of ``block``, ``B`` weighted refits from the block EM's answer, which itself
+        starts at the engine's own P heads and the encoder's final Q.  One ``BootResult`` per head; the engine's parameters and
+        optimiser state are left as they are."""
+        from . import bootstrap
+        self._analysis("bootstrap_q", "use bootstrap.bootstrap_q on one GPU from the written .P and .Q files")
+        return bootstrap.bootstrap_q(self.xp, self.M, [self.P(h) for h in range(len(self.lay.ks))],
+                                     final_q(self, int(self.xp.shape[0]), self.bmax), B, block, rounds, tol, seed)
+
     def kinship(self, head: int = 0, min_phi: Optional[float] = None, pimin: float = 0.0):
         """Admixture-aware kinship (REAP) of the resident matrix's samples from head ``head``'s P and the encoder's final Q
         (relate.kinship_pairs; include/nadm.h, nadm_kinship): ``(i, j, phi, n, inbreeding)``, the pairs i < j with phi >= ``min_phi``

@@ -45,6 +45,7 @@ class Q_P:
         self.ks_list = [int(k) for k in ks_list]
         self.engine = engine
         self.full_params = full_params       # SNP-sharded runs: {"V": [M,C], "P": [[M,k] ...]} gathered on the master
+        self.boot_results: Optional[list] = None   # train(..., bootstrap=B) leaves one bootstrap.BootResult per head here
         self._pending = None
         if engine is None and V is not None:
             self._pending = {"V": V}

@@ -27,18 +27,33 @@ POLISH_ROWS = 1024   # rows per Q step of polish(): bounds nadm_project_scratch_
 
 def em_step(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor], b: int, Pp: torch.Tensor, k: int, qin: torch.Tensor,
             qout: torch.Tensor, scratch: torch.Tensor, eps: float = EPS, qmin: float = QMIN,
-            loglik: Optional[torch.Tensor] = None, nobs: Optional[torch.Tensor] = None) -> None:
-    """One ``nadm_project_q`` call on the current stream: ``Pp [M, kp]``, ``qin`` / ``qout [b, kp]`` (may be the same tensor)."""
+            loglik: Optional[torch.Tensor] = None, nobs: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None) -> None:
+    """One ``nadm_project_q`` call on the current stream: ``Pp [M, kp]``, ``qin`` / ``qout [b, kp]`` (may be the same tensor).
+    ``weights``: a uint8 device vector of M SNP weights (``check_weights``) makes it one ``nadm_project_q_w`` call instead."""
     kp = Pp.shape[1]
+    if weights is not None:
+        if weights.dtype != torch.uint8 or weights.device != xp.device or weights.dim() != 1 or weights.shape[0] != M or not weights.is_contiguous():
+            raise RuntimeError(f"weights must be a contiguous uint8 vector of {M} entries on the matrix's device")
+        check(lib.nadm_project_q_w(ptr(xp), xp.shape[1], ptr(idx), b, M, ptr(Pp), k, kp, ptr(qin), ptr(qout), qin.stride(0),
+                                   eps, qmin, ptr(loglik), ptr(nobs), ptr(scratch), ptr(weights), _stream()), "project_q_w")
+        return
     check(lib.nadm_project_q(ptr(xp), xp.shape[1], ptr(idx), b, M, ptr(Pp), k, kp, ptr(qin), ptr(qout), qin.stride(0),
                              eps, qmin, ptr(loglik), ptr(nobs), ptr(scratch), _stream()), "project_q")
 
 
+def check_weights(weights: torch.Tensor, M: int) -> None:
+    """The refusal the weighted Q step leaves to this layer: a sample's count of observed calls is an int32 sum of weights, so the
+    weights of all M SNPs together must stay below 2^31 (one device reduction and one host read: once per fit, not per step)."""
+    if int(weights.sum(dtype=torch.int64)) > 0x7FFFFFFF:
+        raise RuntimeError("the SNP weights sum to more than 2^31 - 1")
+
+
 def refine_heads(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor], b: int, Pps: Sequence[torch.Tensor], ks: Sequence[int],
-                 q0s: Sequence[torch.Tensor], iters: int, tol: float, eps: float = EPS, qmin: float = QMIN, with_loglik: bool = False):
+                 q0s: Sequence[torch.Tensor], iters: int, tol: float, eps: float = EPS, qmin: float = QMIN, with_loglik: bool = False,
+                 weights: Optional[torch.Tensor] = None):
     """The iteration both public forms share.  ``Pps[h] [M, kp_h]``, ``q0s[h] [b, kp_h]`` (not modified).  Stops after ``iters``
     steps, or earlier once ``max |q_out - q_in| < tol`` over the batch and ALL heads (one device reduction and one host read per
-    iteration).  Returns ``(Qs [b, kp_h], lls, nobs, iterations run)``; ``lls`` (float64 [b], at the returned Q) and ``nobs``
+    iteration).  ``weights``: SNP weights for every step (``em_step``).  Returns ``(Qs [b, kp_h], lls, nobs, iterations run)``; ``lls`` (float64 [b], at the returned Q) and ``nobs``
     (int32 [b]) per head, or None without ``with_loglik``."""
     check_packed(xp, idx, b)
     dev = xp.device
@@ -50,7 +65,7 @@ def refine_heads(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor], b: int, 
     for _ in range(int(iters)):
         delta = None
         for h, Pp in enumerate(Pps):
-            em_step(xp, M, idx, b, Pp, ks[h], cur[h], nxt[h], scratch, eps, qmin)
+            em_step(xp, M, idx, b, Pp, ks[h], cur[h], nxt[h], scratch, eps, qmin, weights=weights)
             d = (nxt[h] - cur[h]).abs().max()
             delta = d if delta is None else torch.maximum(delta, d)
         cur, nxt = nxt, cur
@@ -63,7 +78,7 @@ def refine_heads(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor], b: int, 
         for h, Pp in enumerate(Pps):
             ll = torch.empty(b, dtype=torch.float64, device=dev)
             no = torch.empty(b, dtype=torch.int32, device=dev)
-            em_step(xp, M, idx, b, Pp, ks[h], cur[h], nxt[h], scratch, eps, qmin, ll, no)
+            em_step(xp, M, idx, b, Pp, ks[h], cur[h], nxt[h], scratch, eps, qmin, ll, no, weights=weights)
             lls.append(ll)
             nobs.append(no)
     return cur, lls, nobs, done
@@ -115,24 +130,30 @@ def project_p(xp: torch.Tensor, M: int, Q, p0=None, iters: int = 20, tol: float 
     return cur[:, :K].clone()
 
 
-def _summed_loglik(xp: torch.Tensor, M: int, N: int, Pps, ks, Qps, rows: int, eps: float, qmin: float) -> float:
+def _summed_loglik(xp: torch.Tensor, M: int, N: int, Pps, ks, Qps, rows: int, eps: float, qmin: float, weights=None) -> float:
     """Log-likelihood of the observed calls summed over the rows 0..N and the heads, in float64: the ``ll`` of a Q step that moves
     nothing (``refine_heads`` with ``iters = 0``), in row batches."""
     total = 0.0
     for s in range(0, N, rows):
         bb = min(rows, N - s)
-        _, lls, _, _ = refine_heads(xp[s:s + bb], M, None, bb, Pps, ks, [q[s:s + bb] for q in Qps], 0, 0.0, eps, qmin, with_loglik=True)
+        _, lls, _, _ = refine_heads(xp[s:s + bb], M, None, bb, Pps, ks, [q[s:s + bb] for q in Qps], 0, 0.0, eps, qmin, with_loglik=True,
+                                     weights=weights)
         total += float(sum(ll.sum() for ll in lls))
     return total
 
 
 def polish(xp: torch.Tensor, M: int, Ps: Sequence, Qs: Sequence, rounds: int, tol: float = 1e-5, eps: float = EPS, qmin: float = QMIN,
-           pmin: float = PMIN):
+           pmin: float = PMIN, weights: Optional[torch.Tensor] = None):
     """Block EM over the observed calls from a given answer: per head ``h``, ``Ps[h] [M, k_h]`` and ``Qs[h] [N, k_h]`` (host or device;
     N = the rows of ``xp``) are alternately refitted -- one round is a Q step over all rows with P fixed (in batches of POLISH_ROWS
     rows), then a P step over all rows with the new Q -- for ``rounds`` rounds, or until max |dQ| and max |dP| of a round are both
     below ``tol`` over all heads.  Returns ``(Ps, Qs, ll_before, ll_after, rounds_run)``: float32 device matrices ``[M, k_h]`` /
-    ``[N, k_h]`` and the log-likelihood of the observed calls summed over samples and heads (float64) at the start and at the end."""
+    ``[N, k_h]`` and the log-likelihood of the observed calls summed over samples and heads (float64) at the start and at the end.
+    ``weights`` (a uint8 device vector of M entries, e.g. a bootstrap replicate's ``bootstrap.block_weights``) makes it the block EM of
+    the weighted likelihood sum_j w_j l_j: every Q step and both log-likelihoods carry the weights; the P step needs none (a SNP's
+    weight multiplies its numerator and denominator alike).  ``None`` is the unweighted call path as it always was."""
+    if weights is not None:
+        check_weights(weights, M)
     N, dev = n_rows(xp, None), xp.device
     if any(np.shape(P)[0] != M for P in Ps):
         raise RuntimeError(f"every P must have {M} rows, one per SNP")
@@ -140,7 +161,7 @@ def polish(xp: torch.Tensor, M: int, Ps: Sequence, Qs: Sequence, rounds: int, to
     rows = min(POLISH_ROWS, N)
     q_scratch = torch.empty(max(max(int(lib.nadm_project_scratch_floats(rows, M, Pp.shape[1])) for Pp in Pc), 4), dtype=torch.float32, device=dev)
     p_scratch = _p_scratch(N, M, [Pp.shape[1] for Pp in Pc], dev)
-    ll_before = _summed_loglik(xp, M, N, Pc, ks, Qc, rows, eps, qmin)
+    ll_before = _summed_loglik(xp, M, N, Pc, ks, Qc, rows, eps, qmin, weights)
     done = 0
     for _ in range(int(rounds)):
         delta = torch.zeros((), dtype=torch.float32, device=dev)
@@ -148,12 +169,12 @@ def polish(xp: torch.Tensor, M: int, Ps: Sequence, Qs: Sequence, rounds: int, to
             qn, pn = torch.empty_like(Qc[h]), torch.empty_like(Pc[h])
             for s in range(0, N, rows):
                 bb = min(rows, N - s)
-                em_step(xp[s:s + bb], M, None, bb, Pc[h], k, Qc[h][s:s + bb], qn[s:s + bb], q_scratch, eps, qmin)
+                em_step(xp[s:s + bb], M, None, bb, Pc[h], k, Qc[h][s:s + bb], qn[s:s + bb], q_scratch, eps, qmin, weights=weights)
             p_step(xp, M, None, N, qn, k, Pc[h], pn, p_scratch, eps, pmin)
             delta = torch.maximum(delta, torch.maximum((qn - Qc[h]).abs().max(), (pn - Pc[h]).abs().max()))
             Qc[h], Pc[h] = qn, pn
         done += 1
         if float(delta) < tol:
             break
-    ll_after = _summed_loglik(xp, M, N, Pc, ks, Qc, rows, eps, qmin) if done else ll_before
+    ll_after = _summed_loglik(xp, M, N, Pc, ks, Qc, rows, eps, qmin, weights) if done else ll_before
     return [P[:, :k].clone() for P, k in zip(Pc, ks)], [Q[:, :k].clone() for Q, k in zip(Qc, ks)], ll_before, ll_after, done

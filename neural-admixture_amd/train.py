@@ -223,7 +223,7 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
           num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
           n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto", precision: str = "highest",
           unlabelled=None, supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5, cv: int = 0,
-          cv_rounds: int = 50, cv_tol: float = 1e-5):
+          cv_rounds: int = 50, cv_tol: float = 1e-5, bootstrap: int = 0, boot_block: int = 1, boot_rounds: int = 50, boot_tol: float = 1e-5):
     """The reference's boundary function (see the module docstring and _train).  The host thread pools (torch intra-op, BLAS,
     OpenMP) are capped at ``host_threads`` while it runs -- the reference's CLI does that with --threads (entry.py:138-146), and
     this package's CLI passes its --threads here; the epoch loop itself always runs with torch's pool at 1 (model.py).
@@ -242,7 +242,12 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
     ``cv`` / ``cv_rounds`` / ``cv_tol`` (keyword, CLI --cv / --cv_rounds / --cv_tol): after training -- and after polishing, where
     ``polish`` is given -- the cross-validation error of every K over ``cv`` folds of held-out CALLS (cv.cv_error, fold seed
     ``seed``), refitted from the matrices about to be returned, is logged as ``CV error (K=k): x``.  Single-GPU, unsupervised runs
-    only; 0 (the default) calls nothing."""
+    only; 0 (the default) calls nothing.
+    ``bootstrap`` / ``boot_block`` / ``boot_rounds`` / ``boot_tol`` (keyword, CLI --bootstrap / --block / --boot_rounds / --boot_tol):
+    after all of the above, bootstrap standard errors of every K's Q from ``bootstrap`` replicates that resample the SNPs in blocks
+    of ``boot_block`` (bootstrap.bootstrap_q, draw seed ``seed``), refitted from the matrices about to be returned; logged, and left
+    in the returned model's ``boot_results`` (None without it; the CLI writes them as .Q_se / .Q_bias).  Single-GPU, unsupervised
+    runs only; 0 (the default) calls nothing."""
     if precision not in PRECISIONS:
         raise ValueError("precision must be 'highest' or 'medium'")
     if polish < 0:
@@ -255,18 +260,24 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
         raise ValueError("cv_rounds must be >= 1")
     if cv > 0 and (num_gpus > 1 or pops is not None):
         raise ValueError("cv needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
+    if bootstrap != 0 and bootstrap < 2:
+        raise ValueError("bootstrap must be 0 or a number of replicates >= 2")
+    if bootstrap > 0 and (boot_rounds < 1 or boot_block < 1):
+        raise ValueError("boot_rounds and boot_block must be >= 1")
+    if bootstrap > 0 and (num_gpus > 1 or pops is not None):
+        raise ValueError("bootstrap needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
     with capped_host_threads(max(1, int(host_threads))):
         return _train(epochs, batch_size, learning_rate, K, seed, data, device, num_gpus, hidden_size, master, V, pops, min_k, max_k,
                       n_components, parallelism=parallelism, gmm=gmm, precision=precision, unlabelled=unlabelled,
                       supervised_loss_weight=supervised_loss_weight, polish=polish, polish_tol=polish_tol, cv=cv, cv_rounds=cv_rounds,
-                      cv_tol=cv_tol)
+                      cv_tol=cv_tol, bootstrap=bootstrap, boot_block=boot_block, boot_rounds=boot_rounds, boot_tol=boot_tol)
 
 
 def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
            num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
            n_components: int = None, *, parallelism: str = "dp", gmm: str = "auto", precision: str = "highest", unlabelled=None,
            supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5, cv: int = 0, cv_rounds: int = 50,
-           cv_tol: float = 1e-5):
+           cv_tol: float = 1e-5, bootstrap: int = 0, boot_block: int = 1, boot_rounds: int = 50, boot_tol: float = 1e-5):
     """See module docstring.  ``data`` uint8 [N,M] CPU tensor (or an ``io.PackedGenotypes``, e.g. from
     ``io.read_bed_packed``); ``V`` numpy [C,M] (RSVD output,
     svd.py:83); returns Ps (list of [M,k] float32), Qs (list of [N,k] float32), model.
@@ -338,6 +349,11 @@ def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int
     if cv > 0:                                             # on the matrices about to be returned
         from . import cv as _cv
         _cv.log_results(_cv.cv_error(model.engine.xp, M, Ps, Qs, cv, cv_rounds, cv_tol, seed), log)
+        log.info("")
+    if bootstrap > 0:                                      # likewise; the written .Q stays the one above, the centre goes with the results
+        from . import bootstrap as _boot
+        raw.boot_results = _boot.bootstrap_q(model.engine.xp, M, Ps, Qs, bootstrap, boot_block, boot_rounds, boot_tol, seed)
+        _boot.log_results(raw.boot_results, log, boot_rounds)
         log.info("")
     if master:
         ks = [K] if K is not None else list(range(min_k, max_k + 1))
