@@ -764,6 +764,47 @@ int nadm_cv_deviance(const uint8_t* xp, int64_t ld, int32_t b, int64_t row0, int
                      uint64_t seed, int32_t folds, int32_t fold,
                      double* dev, int32_t* nheld, float* scratch, void* stream);
 
+/* ---- Standard errors of P: the per-SNP Fisher information of a SNP's frequency row GIVEN the ancestry fractions ------------------
+ * The sampling error of p_jk comes from the sample axis: from how many allele copies of ancestry k were observed at SNP j.  One
+ * call = the rows idx[0..b) (idx == NULL: rows 0..b; any order, a duplicate counts as often as it occurs), Q [b, k] (row s belongs
+ * to idx[s], row stride q_stride, a multiple of 4, >= kp, pad cols 0) and ONE head P [M, kp] (kp = nadm_pad_k(k), pad cols 0).
+ * Codes g in {0, 1, 2} are observed, 3 is missing:
+ *     pi_ij  = sum_k q_ik p_jk                                      (fp32, fused multiply-adds, k in order, as nadm_snp_hwe)
+ *     m_ij   = 1 if the call is observed and j < M, else 0
+ *     r = clip(pi, eps, 1 - eps);   u = clip(1 - pi, eps, 1 - eps)  (u from the UNCLIPPED pi, as nadm_project_p)
+ *     w_ij   = m_ij 2 / (r u)                                       (the Fisher information of pi in one binomial(2, pi) call)
+ *     I_j[a][c] = sum_i w_ij q_ia q_ic   for a <= c < k             n_j = sum_i m_ij
+ * This is the EXPECTED information of the row p_j., not the observed one (weight g / pi^2 + (2 - g) / (1 - pi)^2): its weight does
+ * not depend on the call's value -- replacing observed codes by other observed codes leaves every output bit unchanged -- and it is
+ * bounded by 2 / eps where the observed weight reaches 1 / eps^2, which an fp32 running sum needs; the two calibrate alike (DESIGN.md
+ * 4.14).  The caller inverts I_j over the SNP's free components in float64: SE_jk = sqrt((I_j^-1)_kk), CONDITIONAL on Q.
+ * info double [M, k (k + 1) / 2]: the pairs a <= c of the real columns, a-major ((0,0), (0,1), .., (0,k-1), (1,1), ..); nobs int32
+ * [M].  k <= 16 (kp in {4, 8, 12, 16}): the kp (kp + 1) / 2 running sums of a SNP live in one thread's registers; a wider head is
+ * refused.  eps in [1e-9, 0.5).  scratch: nadm_snp_info_scratch_floats(b, M, kp) floats (grows with b, with M and with kp; 0 for a
+ * kp without a kernel).  xp, Q, P, scratch 16-byte, info 8-byte, nobs, idx 4-byte aligned; ld >= ceil(M/4), ld % 16 == 0, ld < 2^32.
+ * A missing call, a row past the list and a SNP >= M enter every sum as exactly +0.0f / 0 (the result does not depend on the pad
+ * bits of a row's last byte, nor on P at a SNP nobody observes -- a NaN there included); an entry whose every term is 0 comes out as
+ * +0.0.  1 / (r u) is one multiplication and the hardware's 1-ulp reciprocal; w q_a is rounded once, then fused multiply-adds.  The
+ * batch's 64-sample tiles are cut into nadm_snp_info_slices(b, M) slices of whole tiles (the rule of nadm_snp_hwe_slices; never more
+ * than 4096 samples in one slice): the sums are fp32 within a slice in sample order, the slices' partials are added in float64 in
+ * slice order and the factor 2 is applied once, there (exact); n is an integer sum, exact.  The order depends on (b, M) alone and
+ * there are no floating-point atomics: the same inputs give the same bits.  Every refusal -- a null pointer, an empty block, ld, k
+ * and kp, q_stride, eps, k > 16, alignment -- is reported before anything is launched.  Asynchronous on `stream`.
+ *
+ * nadm_snp_info_se: the float64 inverse, one thread per SNP.  info [M, k (k + 1) / 2] and nobs [M] as nadm_snp_info writes them, drop
+ * uint8 [M, k] (nonzero: the component is not free -- fixed at the boundary or unseen; the caller's rule), se double [M, k] out, all
+ * on the device.  The rows and columns of a SNP's dropped components are replaced by those of the identity, the block is factored
+ * as L L^T (a pivot s is accepted if s > 0, as LAPACK's potrf does) and (I^-1)_cc = |L^-1 e_c|^2 comes from one forward substitution
+ * per column; se_jc = sqrt of it.  NaN: a dropped component; every entry of a SNP with nobs = 0 or with a pivot that is not > 0
+ * (the free block is not positive definite in float64).  Plain IEEE float64 arithmetic in a fixed order: the same inputs give the
+ * same bits.  1 <= k <= 16; info, se 8-byte, nobs 4-byte aligned; refusals are reported before the launch. */
+int32_t nadm_snp_info_slices(int32_t b, int64_t M);
+int64_t nadm_snp_info_scratch_floats(int32_t b, int64_t M, int32_t kp);
+int nadm_snp_info(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                  const float* Q, int32_t q_stride, int32_t k, int32_t kp, const float* P,
+                  float eps, double* info, int32_t* nobs, float* scratch, void* stream);
+int nadm_snp_info_se(const double* info, const uint8_t* drop, const int32_t* nobs, int64_t M, int32_t k, double* se, void* stream);
+
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,
  * random_state=seed).fit(X).means_): the EM iterations of that call in float64 on the host (csrc/nadm_gmm.cpp restates the

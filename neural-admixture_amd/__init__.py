@@ -16,8 +16,9 @@ from .ld import snp_counts, ld_band, prune, select_snps    # noqa: F401  (LD pru
 from .hwe import snp_hwe, snp_hwe_sums, hwe_keep    # noqa: F401  (Hardy-Weinberg score test given ancestry, per SNP, from Q and P)
 from .cv import cv_error, mask_fold, heldout_deviance    # noqa: F401  (cross-validation error for choosing K, over held-out calls)
 from .bootstrap import bootstrap_q, block_weights    # noqa: F401  (bootstrap standard errors of Q: SNPs resampled, weighted refits)
+from .pse import p_se, p_info, se_from_info    # noqa: F401  (standard errors of P: per-SNP Fisher information given Q, inverted)
 from . import pack2bit            # noqa: F401  (the reference's native module by its own names: pack2bit.cu:144-147)
 
 __all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish", "kinship", "kinship_pairs",
            "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep", "cv_error", "mask_fold", "heldout_deviance",
-           "bootstrap_q", "block_weights"]
+           "bootstrap_q", "block_weights", "p_se", "p_info", "se_from_info"]

@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv|bootstrap ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv|bootstrap|pse ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -88,6 +88,10 @@ def parse_train_args(argv):
                         "the SNPs, refitted from the matrices about to be written: {name}.{K}.Q_se and .Q_bias like ADMIXTURE's -B; "
                         "the draw uses --seed.  Single-GPU, unsupervised runs only.  0 (default): off")
     _add_boot_refit(p)
+    p.add_argument("--p_se", action="store_true",
+                   help="after training (and after --polish), standard errors of every K's P from the per-SNP Fisher information given "
+                        "the Q about to be written: {name}.{K}.P_se, M x K like the .P file, nan where no standard error is defined.  "
+                        "Conditional on Q; every K must be <= 16.  Single-GPU, unsupervised runs only")
     _add_precision(p)
     _add_extract(p)
     return p.parse_args(argv)
@@ -197,6 +201,18 @@ def parse_bootstrap_args(argv):
     p.add_argument("-B", "--replicates", type=int, default=200, help="bootstrap replicates (default 200, ADMIXTURE's)")
     _add_boot_refit(p)
     p.add_argument("--seed", type=int, default=42, help="seed of the draw")
+    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
+    p.add_argument("--threads", type=int, default=1)
+    _add_extract(p)
+    return p.parse_args(argv)
+
+
+def parse_pse_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture pse",
+                                description="Standard errors of P: the per-SNP Fisher information given Q, from a run's .P and .Q files")
+    _add_run_heads(p)
+    p.add_argument("--bound", type=float, default=1e-4,
+                   help="a frequency within this of 0 or 1 is taken as fixed at the boundary and gets no standard error (default 1e-4)")
     p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
     p.add_argument("--threads", type=int, default=1)
     _add_extract(p)
@@ -453,6 +469,32 @@ def _bootstrap_main(argv, t0):
     return 0
 
 
+def _check_pse_ks(ks, flag):
+    """The check `pse` and `train --p_se` share: the K list came with ``flag``."""
+    if max(ks) > 16:
+        raise SystemExit(f"    {flag} needs every K <= 16: the K (K + 1) / 2 running sums of a SNP live in one thread's registers "
+                         f"(K = {max(ks)} was asked for).")
+
+
+def _pse_main(argv, t0):
+    """``pse`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.P_se (M x K, the .P text
+    format, nan where no standard error is defined) and one ``P standard errors (K=k)`` line per K in the log."""
+    from . import pse
+    args = parse_pse_args(argv)
+    ks = _ks_asked(args)
+    _check_pse_ks(ks, "pse")
+    if not 0.0 <= args.bound < 0.5:
+        raise SystemExit("    --bound must be in [0, 0.5).")
+    data, Ps, Qs = _read_run_heads(args, ks, "pse")
+    log.info(f"    Standard errors of P given Q (expected Fisher information per SNP; fixed within {args.bound:g} of 0 or 1).")
+    results = [pse.p_se(data.packed, data.M, P, Q, bound=args.bound) for P, Q in zip(Ps, Qs)]
+    pse.log_results(results, log)
+    pse.write_results(args.save_dir, args.out_name or args.name, results)
+    log.info("    Standard errors of P saved.")
+    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
+    return 0
+
+
 def _kinship_main(argv, t0):
     """``kinship`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.kin (``i j phi n`` per related pair, 0-based
     sample indices, by i then j) and {out_name}.{k}.inbreed (one inbreeding coefficient per sample)."""
@@ -541,13 +583,17 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
                           host_threads=args.threads, gmm=args.gmm, precision=args.precision,
                           unlabelled=None if pops is None else (args.unlabelled,), supervised_loss_weight=args.supervised_loss_weight,
                           polish=args.polish, polish_tol=args.polish_tol, cv=args.cv, cv_rounds=args.cv_rounds, cv_tol=args.cv_tol,
-                          bootstrap=args.bootstrap, boot_block=args.block, boot_rounds=args.boot_rounds, boot_tol=args.boot_tol)
+                          bootstrap=args.bootstrap, boot_block=args.block, boot_rounds=args.boot_rounds, boot_tol=args.boot_tol,
+                          p_se=args.p_se)
     if master:
         save_model(model, args.name, args.save_dir)
         write_outputs(Qs, args.name, K, args.min_k, args.max_k, args.save_dir, Ps)
         if args.bootstrap > 0:
             from .bootstrap import write_results
             write_results(args.save_dir, args.name, model.boot_results)
+        if args.p_se:
+            from .pse import write_results as write_pse
+            write_pse(args.save_dir, args.name, model.pse_results)
         log.info("    Q and P matrices saved." if K is not None else "    Q and P matrices saved for all K.")
         log.info("")
         log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
@@ -555,14 +601,15 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
         torch.distributed.destroy_process_group()
 
 
-_ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main}
+_ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
+                   "pse": _pse_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv", "bootstrap"), \
+    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv", "bootstrap", "pse"), \
         ('Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions, '
-         '"cv" helps to choose K, "bootstrap" puts standard errors on Q).')
+         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         return _ANALYSIS_MODES[mode](argv[1:], t0)
@@ -580,6 +627,13 @@ def main(argv=None):
                 raise SystemExit("    --bootstrap is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
             if args.pops_path:
                 raise SystemExit("    --bootstrap ignores labels: it is not available with --pops_path (supervised runs).")
+        if args.p_se:
+            if args.num_gpus > 1:
+                raise SystemExit("    --p_se is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
+            if args.pops_path:
+                raise SystemExit("    --p_se ignores labels: it is not available with --pops_path (supervised runs).")
+            if args.k is not None or args.max_k is not None:
+                _check_pse_ks([args.k if args.k is not None else args.max_k], "--p_se")
     _need_gpu()
     if mode == "train":
         assert args.epochs > 0 and args.batch_size > 0 and args.learning_rate > 0 and args.hidden_size > 0 and args.n_components > 0

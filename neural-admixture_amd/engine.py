@@ -619,6 +619,18 @@ class Engine:
         self._analysis("snp_hwe", "use hwe.snp_hwe on one GPU from the written .P and .Q files", head=head)
         return hwe.snp_hwe(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], pimin=pimin)
 
+    def p_se(self, head: int = 0, bound: float = 1e-4):
+        """Standard errors of head ``head``'s P, per SNP and component of the resident matrix, from the Fisher information given the
+        encoder's final Q (pse.p_se; include/nadm.h, nadm_snp_info): a ``PseResult`` with ``se, n_eff`` (float64 ``[M, K]``, NaN
+        where a component is within ``bound`` of 0 or 1, unseen, or the SNP's block is singular), ``n`` (int32 ``[M]``) and the
+        ``fixed`` / ``unseen`` patterns.  Conditional on Q; K <= 16.  The engine's parameters and optimiser state are left as they
+        are."""
+        from . import pse
+        self._analysis("p_se", "use pse.p_se on one GPU from the written .P and .Q files", head=head)
+        if self.lay.ks[head] > pse.MAX_K:
+            raise RuntimeError(f"Engine.p_se: {pse.TOO_WIDE}")
+        return pse.p_se(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], bound=bound)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()
