@@ -805,6 +805,64 @@ int nadm_snp_info(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, 
                   float eps, double* info, int32_t* nobs, float* scratch, void* stream);
 int nadm_snp_info_se(const double* info, const uint8_t* drop, const int32_t* nobs, int64_t M, int32_t k, double* se, void* stream);
 
+/* ---- Model-fit check: the pairwise correlation of leave-one-out residuals (evalAdmix, Garcia-Erill & Albrechtsen 2020) -----------
+ * Does the model describe these samples, and if not, which ones?  Under a good fit the residuals g - 2 pi of two samples are
+ * uncorrelated; where the model is wrong the correlation is positive inside the groups it merged or mis-modelled and negative
+ * between them.  A sample's own genotype sits in the frequencies its residual is taken against, which biases a pair inside a group of
+ * n unadmixed samples by about -1/n; the correction refits the frequencies WITHOUT one sample of the pair -- one EM step of P from
+ * the sums nadm_project_p forms -- and takes BOTH residuals against that refit.
+ *
+ * nadm_em_sums: the sums themselves, in nadm_project_p's notation and with its arguments: for the rows idx[0..b) (idx == NULL: rows
+ * 0..b; a duplicate counts as often as it occurs), Q [b, k] and ONE head P [M, kp],
+ *     B_jk = sum over observed i of q_ik g_ij / r_ij          C_jk = sum over observed i of q_ik (2 - g_ij) / u_ij
+ * written as float [M, kp] each (pad columns 0; rows >= M are never written); nobs_snp int32 [M] may be NULL.  The accumulation is
+ * nadm_project_p's own (one body, csrc/nadm_em_accum.h): fp32 within each of nadm_em_sums_slices(b, M) slices of whole 64-sample
+ * tiles in sample order, the slices' partials added in float64 in slice order and rounded to fp32 ONCE.  Each term is
+ * fma(q_ik, t, sum) with t1 = g * rcp(r), t0 = (2 - g) * rcp(u) (the hardware's 1-ulp reciprocal); a missing call and a SNP >= M
+ * enter as exactly +0.0f.  scratch: nadm_em_sums_scratch_floats(b, M, kp) floats.  xp, Q, P, B, C, scratch 16-byte aligned.
+ *
+ * nadm_resid_cor: one block of ORDERED pairs, the rows idxA[0..ba) against the LEFT-OUT rows idxB[0..bb) (idx == NULL: rows 0..b; any
+ * order, duplicates allowed, the lists may overlap or be the same), QA [ba, k] / QB [bb, k] as in nadm_kinship, ONE head P [M, kp],
+ * and B, C float [M, kp] as nadm_em_sums wrote them over ALL rows of the fit (the rows of idxB among them).  For a left-out sample
+ * b observed at SNP j (t1, t0 of b's own call as above: its terms as they entered the sums), all in fp32, every operation rounded
+ * on its own (no contraction) unless written fma:
+ *     beta_k = q_bk * t1                 gamma_k = q_bk * t0
+ *     num'   = p_jk * max(B_jk - beta_k, 0)
+ *     den'   = num' + (1 - p_jk) * max(C_jk - gamma_k, 0)
+ *     den    = p_jk * B_jk + (1 - p_jk) * C_jk
+ *     f_jk   = num' / den'  (IEEE division)  if den' >= NADM_LOO_MIN_SHARE * den and den > 0 and den' > 0,   else p_jk
+ * one EM step of P without sample b.  The fallback covers a frequency whose information is mostly b's own (a component that b alone
+ * carries: B - beta = 0): without it the quotient loses all its digits.  NADM_LOO_MIN_SHARE = 1/8 is a design constant, not a
+ * measurement; the three comparisons above, on those fp32 values, decide the branch (den' > 0 differs from the first only where
+ * den / 8 underflows; a NaN compares false and keeps p).  Where b is missing at j, beta = gamma = 0 and nothing of the SNP enters
+ * the pair.  Then for every sample a of the block (a = b included), o = 1 where the call is observed and j < M, else 0:
+ *     pi_aj = sum_k q_ak f_jk   (fused multiply-adds, k in order)        d_aj = o_aj fma(-2, pi_aj, g_aj)
+ *     S_ab  = sum_j d_aj d_bj     Ta_ab = sum_j d_aj^2 o_bj     Tb_ab = sum_j d_bj^2 o_aj     n_ab = sum_j o_aj o_bj
+ * S, Ta, Tb double [ba, bb], n int32 [ba, bb] (may be NULL), row-major.  The caller forms c_ab = S / sqrt(Ta Tb) (none where Ta Tb
+ * = 0) and symmetrises (c_ab + c_ba) / 2: c_ab and c_ba are different computations.  ba, bb in 1..NADM_RESID_COR_MAX_ROWS; k <= 16
+ * (kp in {4, 8, 12, 16}), a wider head is refused; eps in [1e-9, 0.5).  scratch: nadm_resid_cor_scratch_floats(ba, bb, M, kp)
+ * floats, bounded by ranges x ba x bb (padded to tiles), never per chunk.  xp, P, QA, QB, B, C, scratch 16-byte, S, Ta, Tb 8-byte,
+ * n, idxA, idxB 4-byte aligned; ld >= ceil(M/4), ld % 16 == 0, ld < 2^32.
+ * A missing call and a SNP >= M enter every sum as exactly +0.0f (the result does not depend on the pad bits of a row's last
+ * byte, nor on P at a SNP nobody observes); n is exact.  The 256-SNP chunks are cut into nadm_resid_cor_ranges(ba, bb, M, kp)
+ * contiguous ranges (more than one while the block's tiles alone do not fill the chip); a lane's fp32 running sums cover one
+ * range in SNP order and never more than 2^18 SNPs; the ranges' partials are added in float64 in range order.  The order depends
+ * on (ba, bb, M, kp) alone and there are no floating-point atomics: the same inputs give the same bits.  Every refusal is reported
+ * before anything is launched.  Asynchronous on `stream`. */
+#define NADM_RESID_COR_MAX_ROWS 4096
+#define NADM_LOO_MIN_SHARE 0.125f   /* the refit without b is used while it keeps at least this share of the SNP-component's den */
+int32_t nadm_em_sums_slices(int32_t b, int64_t M);
+int64_t nadm_em_sums_scratch_floats(int32_t b, int64_t M, int32_t kp);
+int nadm_em_sums(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                 const float* Q, int32_t q_stride, int32_t k, int32_t kp, const float* P,
+                 float eps, float* B, float* C, int32_t* nobs_snp, float* scratch, void* stream);
+int32_t nadm_resid_cor_ranges(int32_t ba, int32_t bb, int64_t M, int32_t kp);
+int64_t nadm_resid_cor_scratch_floats(int32_t ba, int32_t bb, int64_t M, int32_t kp);
+int nadm_resid_cor(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
+                   const float* P, int32_t k, int32_t kp, const float* QA, const float* QB, int32_t q_stride,
+                   const float* B, const float* C, float eps, double* S, double* Ta, double* Tb, int32_t* nobs,
+                   float* scratch, void* stream);
+
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,
  * random_state=seed).fit(X).means_): the EM iterations of that call in float64 on the host (csrc/nadm_gmm.cpp restates the

@@ -122,6 +122,12 @@ def _load():
         "nadm_snp_info_scratch_floats": (i64, [i32, i64, i32]),
         "nadm_snp_info": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, i32, vp, f32, vp, vp, vp, vp]),
         "nadm_snp_info_se": (C.c_int, [vp, vp, vp, i64, i32, vp, vp]),
+        "nadm_em_sums_slices": (i32, [i32, i64]),
+        "nadm_em_sums_scratch_floats": (i64, [i32, i64, i32]),
+        "nadm_em_sums": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp]),
+        "nadm_resid_cor_ranges": (i32, [i32, i32, i64, i32]),
+        "nadm_resid_cor_scratch_floats": (i64, [i32, i32, i64, i32]),
+        "nadm_resid_cor": (C.c_int, [vp, i64, vp, i32, vp, i32, i64, vp, i32, i32, vp, vp, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp]),
         "nadm_snp_counts": (C.c_int, [vp, i64, vp, i64, i64, vp, vp]),
         "nadm_ld_band": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp]),
         "nadm_select_snps": (C.c_int, [vp, i64, i64, vp, i64, i32, vp, i64, vp]),

@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv|bootstrap|pse ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv|bootstrap|pse|fit ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -92,6 +92,12 @@ def parse_train_args(argv):
                    help="after training (and after --polish), standard errors of every K's P from the per-SNP Fisher information given "
                         "the Q about to be written: {name}.{K}.P_se, M x K like the .P file, nan where no standard error is defined.  "
                         "Conditional on Q; every K must be <= 16.  Single-GPU, unsupervised runs only")
+    p.add_argument("--fit_check", action="store_true",
+                   help="after training (and after --polish), the model-fit check of every K from the matrices about to be written: the "
+                        "pairwise correlation of leave-one-out residuals (evalAdmix's statistic), summarised per group of samples (largest "
+                        "component) in {name}.{K}.cor_pop and per sample in {name}.{K}.cor_sample, as the 'fit' mode writes them.  Run it "
+                        "with --polish: the statistic assumes a P at the fixed point of its own EM step.  Every K must be <= 16; the pairs of "
+                        "at most 4096 samples are taken (a seeded subset above that).  Single-GPU, unsupervised runs only")
     _add_precision(p)
     _add_extract(p)
     return p.parse_args(argv)
@@ -213,6 +219,28 @@ def parse_pse_args(argv):
     _add_run_heads(p)
     p.add_argument("--bound", type=float, default=1e-4,
                    help="a frequency within this of 0 or 1 is taken as fixed at the boundary and gets no standard error (default 1e-4)")
+    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
+    p.add_argument("--threads", type=int, default=1)
+    _add_extract(p)
+    return p.parse_args(argv)
+
+
+def parse_fit_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture fit",
+                                description="Model-fit check: pairwise correlation of leave-one-out residuals (evalAdmix's statistic), "
+                                            "from a run's .P and .Q files")
+    _add_run_heads(p)
+    p.add_argument("--pops_path", type=str, default=None, metavar="FILE",
+                   help="one group label per sample, used only for the summary (default: every sample goes to its largest component, the "
+                        "groups are named 1..K)")
+    p.add_argument("--subsample", type=int, default=0, metavar="S",
+                   help="take the pairs among a seeded subset of S <= 4096 samples (the work grows with S^2; the frequencies are still "
+                        "refitted from every sample).  Needed above 4096 samples.  0 (default): every sample")
+    p.add_argument("--seed", type=int, default=42, help="seed of the --subsample draw")
+    p.add_argument("--matrix", action="store_true", help="also write the S x S matrix of correlations, {out_name}.{K}.cor")
+    p.add_argument("--warn", type=float, default=0.02,
+                   help="log a warning for every group pair whose mean correlation exceeds this in magnitude (default 0.02: a convention, "
+                        "not a calibration -- the spread of a pair's correlation under a good fit is about 1 / sqrt(SNPs both were called at))")
     p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
     p.add_argument("--threads", type=int, default=1)
     _add_extract(p)
@@ -409,9 +437,10 @@ def _ks_asked(args):
     return ks
 
 
-def _read_run_heads(args, ks, mode):
+def _read_run_heads(args, ks, mode, check_n=None):
     """{save_dir}/{name}.{K}.P and .Q of every K + the genotypes in HBM -> (data, Ps, Qs); every file is looked for and read before
-    the GPU check, and a matrix of the wrong shape ends the run, naming its file."""
+    the GPU check, and a matrix of the wrong shape ends the run, naming its file.  ``check_n(N)``: a mode's own check of the sample
+    count, run before the GPU check where the input tells N up front (.bed), else once the genotypes are parsed."""
     name = os.path.basename(args.data_path)
     if ".bed" not in name and ".vcf" not in name:
         raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
@@ -425,7 +454,11 @@ def _read_run_heads(args, ks, mode):
             m_known = int(keep.sum())
     Qs = [read_run_matrix(p, k, n_known) for p, k in zip(Q_paths, ks)]
     Ps = [read_run_matrix(p, k, m_known, "model" if m_known is not None else "data") for p, k in zip(P_paths, ks)]
+    if check_n is not None and n_known is not None:
+        check_n(n_known)
     data = _read_on_gpu(args, keep)
+    if check_n is not None and n_known is None:
+        check_n(data.N)
     for paths, mats, rows in ((Q_paths, Qs, data.N), (P_paths, Ps, data.M)):
         for path, a in zip(paths, mats):
             if a.shape[0] != rows:
@@ -491,6 +524,55 @@ def _pse_main(argv, t0):
     pse.log_results(results, log)
     pse.write_results(args.save_dir, args.out_name or args.name, results)
     log.info("    Standard errors of P saved.")
+    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
+    return 0
+
+
+def _check_fit_ks(ks, flag):
+    """The check `fit` and `train --fit_check` share, in the words of `pse`: the K list came with ``flag``."""
+    if max(ks) > 16:
+        raise SystemExit(f"    {flag} needs every K <= 16: a sample's Q row and a chunk's refitted frequencies live in registers and LDS "
+                         f"(K = {max(ks)} was asked for).")
+
+
+def _fit_main(argv, t0):
+    """``fit`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.cor_pop (a header line of
+    group names, then the G x G mean correlations of leave-one-out residuals), {out_name}.{K}.cor_sample (``mean_cor n_pairs`` per
+    sample), with --matrix {out_name}.{K}.cor (S x S, the .Q text format), and the summary and warning lines per K in the log."""
+    from . import fitcheck
+    args = parse_fit_args(argv)
+    ks = _ks_asked(args)
+    _check_fit_ks(ks, "fit")
+    if not args.warn >= 0.0:
+        raise SystemExit("    --warn must be >= 0.")
+    if args.subsample != 0 and not 2 <= args.subsample <= fitcheck.MAX_ROWS:
+        raise SystemExit(f"    --subsample must be in 2..{fitcheck.MAX_ROWS}.")
+    if args.seed < 0:
+        raise SystemExit("    --seed must be >= 0.")
+    labels = None
+    if args.pops_path is not None:
+        if not os.path.isfile(args.pops_path):
+            raise SystemExit(f"    {args.pops_path} not found.")
+        with open(args.pops_path, "r") as fb:
+            labels = [ln.strip() for ln in fb.read().splitlines()]
+
+    def check_n(n):
+        if labels is not None and len(labels) != n:
+            raise SystemExit(f"    {args.pops_path} lists {len(labels)} labels, the data holds {n} samples.")
+        if n > fitcheck.MAX_ROWS and args.subsample == 0:
+            raise SystemExit(f"    The fit check takes the pairs of at most {fitcheck.MAX_ROWS} samples (its work grows with their square) "
+                             f"and the data holds {n}: pass --subsample S with S <= {fitcheck.MAX_ROWS}.")
+    data, Ps, Qs = _read_run_heads(args, ks, "fit", check_n)
+    pairs = None
+    if args.subsample != 0 and args.subsample < data.N:
+        pairs = np.sort(np.random.default_rng(args.seed).choice(data.N, size=args.subsample, replace=False))
+        log.info(f"    --subsample: the pairs among {args.subsample} of {data.N} samples (seed {args.seed}).")
+    log.info("    Fit check: correlation of leave-one-out residuals; groups are " +
+             ("the labels of --pops_path." if labels is not None else "the samples' largest components."))
+    results = [fitcheck.fit_check(data.packed, data.M, P, Q, labels, pairs) for P, Q in zip(Ps, Qs)]
+    fitcheck.log_results(results, log, args.warn)
+    fitcheck.write_results(args.save_dir, args.out_name or args.name, results, matrix=args.matrix)
+    log.info("    Residual correlations saved.")
     log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
     return 0
 
@@ -584,7 +666,7 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
                           unlabelled=None if pops is None else (args.unlabelled,), supervised_loss_weight=args.supervised_loss_weight,
                           polish=args.polish, polish_tol=args.polish_tol, cv=args.cv, cv_rounds=args.cv_rounds, cv_tol=args.cv_tol,
                           bootstrap=args.bootstrap, boot_block=args.block, boot_rounds=args.boot_rounds, boot_tol=args.boot_tol,
-                          p_se=args.p_se)
+                          p_se=args.p_se, fit_check=args.fit_check)
     if master:
         save_model(model, args.name, args.save_dir)
         write_outputs(Qs, args.name, K, args.min_k, args.max_k, args.save_dir, Ps)
@@ -594,6 +676,9 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
         if args.p_se:
             from .pse import write_results as write_pse
             write_pse(args.save_dir, args.name, model.pse_results)
+        if args.fit_check:
+            from .fitcheck import write_results as write_fit
+            write_fit(args.save_dir, args.name, model.fit_results)
         log.info("    Q and P matrices saved." if K is not None else "    Q and P matrices saved for all K.")
         log.info("")
         log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
@@ -602,14 +687,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 
 _ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
-                   "pse": _pse_main}
+                   "pse": _pse_main, "fit": _fit_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv", "bootstrap", "pse"), \
+    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "fit"), \
         ('Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions, '
-         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P).')
+         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "fit" checks the fit sample by sample).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         return _ANALYSIS_MODES[mode](argv[1:], t0)
@@ -634,6 +719,13 @@ def main(argv=None):
                 raise SystemExit("    --p_se ignores labels: it is not available with --pops_path (supervised runs).")
             if args.k is not None or args.max_k is not None:
                 _check_pse_ks([args.k if args.k is not None else args.max_k], "--p_se")
+        if args.fit_check:
+            if args.num_gpus > 1:
+                raise SystemExit("    --fit_check is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
+            if args.pops_path:
+                raise SystemExit("    --fit_check ignores labels: it is not available with --pops_path (supervised runs).")
+            if args.k is not None or args.max_k is not None:
+                _check_fit_ks([args.k if args.k is not None else args.max_k], "--fit_check")
     _need_gpu()
     if mode == "train":
         assert args.epochs > 0 and args.batch_size > 0 and args.learning_rate > 0 and args.hidden_size > 0 and args.n_components > 0

@@ -631,6 +631,18 @@ class Engine:
             raise RuntimeError(f"Engine.p_se: {pse.TOO_WIDE}")
         return pse.p_se(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], bound=bound)
 
+    def resid_cor(self, head: int = 0, pairs_idx=None, rows: int = 1024):
+        """Model fit along the sample axis: the symmetrised correlation of leave-one-out residuals of the resident matrix's samples
+        from head ``head``'s P and the encoder's final Q (fitcheck.resid_cor; include/nadm.h, nadm_em_sums / nadm_resid_cor):
+        ``(cor float64 [S, S]`` with a NaN diagonal, ``n int32 [S, S])`` for the samples ``pairs_idx`` (default: all of them).  0 for
+        every pair under a good fit; K <= 16.  The engine's parameters and optimiser state are left as they are."""
+        from . import fitcheck
+        self._analysis("resid_cor", "use fitcheck.resid_cor on one GPU from the written .P and .Q files", head=head)
+        if self.lay.ks[head] > fitcheck.MAX_K:
+            raise RuntimeError(f"Engine.resid_cor: {fitcheck.TOO_WIDE}")
+        return fitcheck.resid_cor(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], pairs_idx=pairs_idx,
+                                  rows=rows)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()

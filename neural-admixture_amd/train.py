@@ -224,7 +224,7 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
           n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto", precision: str = "highest",
           unlabelled=None, supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5, cv: int = 0,
           cv_rounds: int = 50, cv_tol: float = 1e-5, bootstrap: int = 0, boot_block: int = 1, boot_rounds: int = 50, boot_tol: float = 1e-5,
-          p_se: bool = False):
+          p_se: bool = False, fit_check: bool = False):
     """The reference's boundary function (see the module docstring and _train).  The host thread pools (torch intra-op, BLAS,
     OpenMP) are capped at ``host_threads`` while it runs -- the reference's CLI does that with --threads (entry.py:138-146), and
     this package's CLI passes its --threads here; the epoch loop itself always runs with torch's pool at 1 (model.py).
@@ -251,7 +251,11 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
     runs only; 0 (the default) calls nothing.
     ``p_se`` (keyword, CLI --p_se): after all of the above, the standard errors of every K's P from the per-SNP Fisher information
     given the Q about to be returned (pse.p_se; every K <= 16); logged, and left in the returned model's ``pse_results`` (None
-    without it; the CLI writes them as .P_se).  Single-GPU, unsupervised runs only; False (the default) calls nothing."""
+    without it; the CLI writes them as .P_se).  Single-GPU, unsupervised runs only; False (the default) calls nothing.
+    ``fit_check`` (keyword, CLI --fit_check): after all of the above, the model-fit check of every K from the matrices about to be
+    returned (fitcheck.fit_check: the correlation of leave-one-out residuals, grouped by largest component; every K <= 16; above
+    4096 samples the pairs of a subset drawn with ``seed``); logged, and left in the returned model's ``fit_results`` (None without
+    it; the CLI writes them as .cor_pop / .cor_sample).  Single-GPU, unsupervised runs only; False (the default) calls nothing."""
     if precision not in PRECISIONS:
         raise ValueError("precision must be 'highest' or 'medium'")
     if polish < 0:
@@ -274,18 +278,24 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
         raise ValueError("p_se needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
     if p_se and max([k for k in ((K,) if K is not None else (max_k,)) if k is not None], default=0) > 16:
         raise ValueError("p_se needs every K <= 16")
+    if fit_check and (num_gpus > 1 or pops is not None):
+        raise ValueError("fit_check needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
+    if fit_check and max([k for k in ((K,) if K is not None else (max_k,)) if k is not None], default=0) > 16:
+        raise ValueError("fit_check needs every K <= 16")
     with capped_host_threads(max(1, int(host_threads))):
         return _train(epochs, batch_size, learning_rate, K, seed, data, device, num_gpus, hidden_size, master, V, pops, min_k, max_k,
                       n_components, parallelism=parallelism, gmm=gmm, precision=precision, unlabelled=unlabelled,
                       supervised_loss_weight=supervised_loss_weight, polish=polish, polish_tol=polish_tol, cv=cv, cv_rounds=cv_rounds,
-                      cv_tol=cv_tol, bootstrap=bootstrap, boot_block=boot_block, boot_rounds=boot_rounds, boot_tol=boot_tol, p_se=p_se)
+                      cv_tol=cv_tol, bootstrap=bootstrap, boot_block=boot_block, boot_rounds=boot_rounds, boot_tol=boot_tol, p_se=p_se,
+                      fit_check=fit_check)
 
 
 def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
            num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
            n_components: int = None, *, parallelism: str = "dp", gmm: str = "auto", precision: str = "highest", unlabelled=None,
            supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5, cv: int = 0, cv_rounds: int = 50,
-           cv_tol: float = 1e-5, bootstrap: int = 0, boot_block: int = 1, boot_rounds: int = 50, boot_tol: float = 1e-5, p_se: bool = False):
+           cv_tol: float = 1e-5, bootstrap: int = 0, boot_block: int = 1, boot_rounds: int = 50, boot_tol: float = 1e-5, p_se: bool = False,
+           fit_check: bool = False):
     """See module docstring.  ``data`` uint8 [N,M] CPU tensor (or an ``io.PackedGenotypes``, e.g. from
     ``io.read_bed_packed``); ``V`` numpy [C,M] (RSVD output,
     svd.py:83); returns Ps (list of [M,k] float32), Qs (list of [N,k] float32), model.
@@ -367,6 +377,13 @@ def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int
         from . import pse as _pse
         raw.pse_results = [_pse.p_se(model.engine.xp, M, P_k, Q_k) for P_k, Q_k in zip(Ps, Qs)]
         _pse.log_results(raw.pse_results, log)
+        log.info("")
+    if fit_check:                                          # likewise: of the P and Q about to be returned
+        from . import fitcheck as _fit
+        n_all = int(model.engine.xp.shape[0])
+        pairs = None if n_all <= _fit.MAX_ROWS else np.sort(np.random.default_rng(seed).choice(n_all, size=_fit.MAX_ROWS, replace=False))
+        raw.fit_results = [_fit.fit_check(model.engine.xp, M, P_k, Q_k, None, pairs) for P_k, Q_k in zip(Ps, Qs)]
+        _fit.log_results(raw.fit_results, log)
         log.info("")
     if master:
         ks = [K] if K is not None else list(range(min_k, max_k + 1))
