@@ -10,6 +10,8 @@
  *   - every call is ASYNCHRONOUS on the hipStream_t passed as `stream` (void*; 0 = null stream)
  *     unless stated otherwise.  (The reference's extension blocks with cudaDeviceSynchronize on the
  *     legacy default stream, pack2bit.cu:115,141; callers that want that behaviour synchronise.)
+ *     ALL device work of a call -- every launch, memset and copy of it -- is issued on `stream`, and the address of row r of
+ *     a packed matrix, r * ld, is formed in 64 bits for any ld < 2^32 (tests/test_placement.py holds both).
  *   - return value: 0 = ok, nonzero = error; nadm_last_error() returns a thread-local message
  *     (the reference raises RuntimeError through TORCH_CHECK, pack2bit.cu:67-76,121-130; the
  *     Python host mirror turns nonzero statuses into RuntimeError).

@@ -44,6 +44,23 @@ def row_ranges(n: int, b: int):
     return [(s, min(b, n - s)) for s in range(0, n, b)]
 
 
+def checked_row_stride(M: int, ld: Optional[int]) -> int:
+    """The row stride in bytes of an engine's packed matrix: ``ld``, or ``ModelLayout.row_stride(M)`` where it is None.  A stride
+    of the caller's own (a matrix with room behind every row, a view of a wider one) must be a multiple of 16, hold a row and fit the
+    ABI's 32 bits (include/nadm.h: row addresses are formed in 64 bits for any ld < 2^32)."""
+    least = ModelLayout.row_stride(M)
+    if ld is None:
+        return least
+    ld = int(ld)
+    if ld % 16 != 0:
+        raise ValueError(f"ld must be a multiple of 16 bytes, got {ld}")
+    if ld < least:
+        raise ValueError(f"ld must be at least the row stride of {int(M)} SNPs, {least} bytes, got {ld}")
+    if ld >= 1 << 32:
+        raise ValueError(f"ld must be below 2^32 bytes, got {ld}")
+    return ld
+
+
 def final_q(eng, n: int, b: int) -> List[torch.Tensor]:
     """The encoder's Q of the rows 0..n of ``eng``'s resident matrix, per head ``[n, k]``: ``eng.infer_q`` on ``row_ranges(n, b)``,
     one after the other.  (A function, not a method: any object with ``device`` and ``infer_q`` will do.)"""
@@ -61,7 +78,7 @@ class Engine:
 
     def __init__(self, M: int, C_: int, Hd: int, ks: Sequence[int], device: torch.device, max_batch: int,
                  mode: str = "single", comm=None, n_buckets: int = 1, comm_a=None, p3_whole: bool = False, debug: bool = False,
-                 precision: str = "highest"):
+                 precision: str = "highest", ld: Optional[int] = None):
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'highest' or 'medium'")
         if not self.supports(device):
@@ -78,7 +95,7 @@ class Engine:
         self.world, self.rank = (comm.world, comm.rank) if comm is not None else (1, 0)
         # "dp": message B = [small | V] travels as n_buckets SNP ranges (csrc/nadm_step.hip); the layout says how many M allows
         self.lay = L = ModelLayout(M, C_, Hd, ks, self.world if mode == "dp" else 1, n_buckets if mode == "dp" else 1)
-        self.M, self.ld = L.M, ModelLayout.row_stride(L.M)
+        self.M, self.ld = L.M, checked_row_stride(L.M, ld)       # ld: the stride of the matrix set_packed will be given (default: compact rows)
         self.bmax = b = int(max_batch)
         z = lambda n, dt=_f32: torch.zeros(int(n), dtype=dt, device=device)
         # parameters and gradients: flat [small | pad | V | P...] (layout.py).  Adam moments: flat like them, except in "dp" mode
@@ -240,6 +257,9 @@ class Engine:
         """uint8 [N,M] CPU tensor -> packed rows in HBM.  Packs on the host (2 bits/genotype cross PCIe instead of 8; the
         reference ships unpacked bytes in 1024-row chunks with a blocking sync per chunk, pack2bit.cu:79-115).  ``rows``:
         optional row selection/order (rank shard)."""
+        if self.ld != ModelLayout.row_stride(self.M):
+            raise RuntimeError(f"pack_from_host packs rows of {ModelLayout.row_stride(self.M)} bytes; this engine was built with ld = {self.ld}: "
+                               "hand it its matrix with set_packed")
         self.rows_are_sharded = rows is not None
         if hasattr(data_u8, "packed"):                   # io.PackedGenotypes: already in the kernel layout, just ship the rows
             if data_u8.M != self.M or data_u8.packed.shape[1] != self.ld:

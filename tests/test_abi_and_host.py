@@ -188,6 +188,27 @@ def test_engine_refuses_cpu_device():
         na.train(1, 8, 1e-3, 3, 0, torch.zeros((4, 100), dtype=torch.uint8), torch.device("cpu"), 0, 16, True, np.zeros((8, 100), np.float32), None)
 
 
+def test_engine_row_stride_check_refuses_in_words():
+    """Engine(ld=...) goes through engine.checked_row_stride (an Engine itself needs a GPU): None is the compact stride; a stride that
+    is no multiple of 16, shorter than a row or beyond the ABI's 32 bits is refused in words; the legal range is taken as it is."""
+    import inspect
+    import neural_admixture_amd as na
+    from neural_admixture_amd.engine import checked_row_stride
+    from neural_admixture_amd.layout import ModelLayout
+    M = 8451
+    least = ModelLayout.row_stride(M)
+    assert least == 2176 and checked_row_stride(M, None) == least and checked_row_stride(M, least) == least
+    assert checked_row_stride(M, 1 << 25) == 1 << 25 and checked_row_stride(M, (1 << 32) - 16) == (1 << 32) - 16
+    assert checked_row_stride(1027, 1 << 31) == 1 << 31
+    for bad, words in ((8, "multiple of 16"), (least - 16, f"at least the row stride of {M} SNPs, {least} bytes"), (2 ** 32, "below 2\\^32"),
+                       (least + 8, "multiple of 16")):
+        with pytest.raises(ValueError, match=words):
+            checked_row_stride(M, bad)
+    sig = inspect.signature(na.Engine.__init__)
+    assert sig.parameters["ld"].default is None and sig.parameters["ld"].kind is inspect.Parameter.POSITIONAL_OR_KEYWORD
+    assert list(sig.parameters)[:7] == ["self", "M", "C_", "Hd", "ks", "device", "max_batch"] and list(sig.parameters)[-1] == "ld"
+
+
 @pytest.mark.parametrize("shape", [(5, 11), (3, 9), (0, 7), (4, 0), (300, 4099), (1, 1)])
 def test_host_packer_bit_exact(shape):
     from neural_admixture_amd._lib import lib, check, ptr
