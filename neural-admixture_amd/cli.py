@@ -13,11 +13,13 @@ import logging
 import os
 import sys
 import time
+from importlib import import_module
 
 import numpy as np
 import torch
 
 from .engine import row_ranges
+from .train import AFTER_KEYWORDS, AFTER_TRAINING
 from .io import chrom_codes, find_run_files, read_bim, read_id_list, read_run_matrix, resolve_ids, write_id_list
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(message)s")
@@ -124,50 +126,52 @@ def parse_infer_args(argv):
     return p.parse_args(argv)
 
 
+def _add_run_args(p, multi_k, out="files"):
+    """What the analysis parsers share: where the data and the run's files are, the K of the run (``multi_k``: --k or --min_k ..
+    --max_k; False: one required --k; None: no K), the host threads and -- unless ``out`` is None -- the output name (of the written
+    ``out``) and --extract."""
+    for flag in ("--data_path", "--save_dir", "--name"):
+        p.add_argument(flag, required=True, type=str)
+    if multi_k is not None:
+        p.add_argument("--k", required=not multi_k, type=int)
+    if multi_k:
+        p.add_argument("--min_k", type=int)
+        p.add_argument("--max_k", type=int)
+    p.add_argument("--threads", type=int, default=1)
+    if out is not None:
+        p.add_argument("--out_name", type=str, default=None, help=f"name of the written {out} (default: --name)")
+        _add_extract(p)
+
+
 def parse_kinship_args(argv):
     p = argparse.ArgumentParser(prog="neural-admixture kinship",
                                 description="Admixture-aware kinship (REAP) of the samples from a run's .P and .Q files")
-    p.add_argument("--data_path", required=True, type=str)
-    p.add_argument("--save_dir", required=True, type=str)
-    p.add_argument("--name", required=True, type=str)
-    p.add_argument("--k", required=True, type=int)
-    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
+    _add_run_args(p, multi_k=False)
     p.add_argument("--min_phi", type=float, default=2.0 ** -4.5,
                    help="list the pairs with a kinship coefficient of at least this (default 0.0442, the lower edge of third-degree relatives)")
     p.add_argument("--pimin", type=float, default=0.0,
                    help="drop a call whose individual-specific allele frequency is outside [pimin, 1 - pimin] (default 0: every observed call counts)")
-    p.add_argument("--threads", type=int, default=1)
-    _add_extract(p)
     return p.parse_args(argv)
 
 
 def parse_prune_args(argv):
     p = argparse.ArgumentParser(prog="neural-admixture prune",
                                 description="LD pruning: the SNPs to keep so that no two within a window have an r^2 above a threshold")
-    p.add_argument("--data_path", required=True, type=str)
-    p.add_argument("--save_dir", required=True, type=str)
-    p.add_argument("--name", required=True, type=str)
+    _add_run_args(p, multi_k=None, out=None)
     p.add_argument("--window", type=int, default=50, help="a SNP is compared with its next window - 1 neighbours on its chromosome (default 50)")
     p.add_argument("--r2", type=float, default=0.1, help="of a pair with an r^2 above this the SNP with the smaller minor-allele frequency goes (default 0.1)")
-    p.add_argument("--threads", type=int, default=1)
     return p.parse_args(argv)
 
 
 def parse_hwe_args(argv):
     p = argparse.ArgumentParser(prog="neural-admixture hwe",
                                 description="Hardy-Weinberg test given ancestry: a per-SNP score test from a run's .P and .Q files")
-    p.add_argument("--data_path", required=True, type=str)
-    p.add_argument("--save_dir", required=True, type=str)
-    p.add_argument("--name", required=True, type=str)
-    p.add_argument("--k", required=True, type=int)
-    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
+    _add_run_args(p, multi_k=False)
     p.add_argument("--pimin", type=float, default=0.0,
                    help="drop a call whose individual-specific allele frequency is outside [pimin, 1 - pimin] (default 0: every observed "
                         "call counts); the score is heavy-tailed for rare variants, 0.01 to 0.05 guards against that")
     p.add_argument("--alpha", type=float, default=1e-6,
                    help="a SNP whose two-sided p-value is below this goes to the .hwe.out list (default 1e-6, plink's customary --hwe threshold)")
-    p.add_argument("--threads", type=int, default=1)
-    _add_extract(p)
     return p.parse_args(argv)
 
 
@@ -190,38 +194,22 @@ def _add_boot_refit(p):
                    help="stop a replicate's refit once no entry of Q or P moves by this much in a round")
 
 
-def _add_run_heads(p):
-    """Where an analysis mode over several K finds a run's files."""
-    p.add_argument("--data_path", required=True, type=str)
-    p.add_argument("--save_dir", required=True, type=str)
-    p.add_argument("--name", required=True, type=str)
-    p.add_argument("--k", type=int)
-    p.add_argument("--min_k", type=int)
-    p.add_argument("--max_k", type=int)
-
-
 def parse_bootstrap_args(argv):
     p = argparse.ArgumentParser(prog="neural-admixture bootstrap",
                                 description="Bootstrap standard errors of Q: SNPs resampled with replacement, from a run's .P and .Q files")
-    _add_run_heads(p)
+    _add_run_args(p, multi_k=True)
     p.add_argument("-B", "--replicates", type=int, default=200, help="bootstrap replicates (default 200, ADMIXTURE's)")
     _add_boot_refit(p)
     p.add_argument("--seed", type=int, default=42, help="seed of the draw")
-    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
-    p.add_argument("--threads", type=int, default=1)
-    _add_extract(p)
     return p.parse_args(argv)
 
 
 def parse_pse_args(argv):
     p = argparse.ArgumentParser(prog="neural-admixture pse",
                                 description="Standard errors of P: the per-SNP Fisher information given Q, from a run's .P and .Q files")
-    _add_run_heads(p)
+    _add_run_args(p, multi_k=True)
     p.add_argument("--bound", type=float, default=1e-4,
                    help="a frequency within this of 0 or 1 is taken as fixed at the boundary and gets no standard error (default 1e-4)")
-    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
-    p.add_argument("--threads", type=int, default=1)
-    _add_extract(p)
     return p.parse_args(argv)
 
 
@@ -229,7 +217,7 @@ def parse_fit_args(argv):
     p = argparse.ArgumentParser(prog="neural-admixture fit",
                                 description="Model-fit check: pairwise correlation of leave-one-out residuals (evalAdmix's statistic), "
                                             "from a run's .P and .Q files")
-    _add_run_heads(p)
+    _add_run_args(p, multi_k=True)
     p.add_argument("--pops_path", type=str, default=None, metavar="FILE",
                    help="one group label per sample, used only for the summary (default: every sample goes to its largest component, the "
                         "groups are named 1..K)")
@@ -241,22 +229,16 @@ def parse_fit_args(argv):
     p.add_argument("--warn", type=float, default=0.02,
                    help="log a warning for every group pair whose mean correlation exceeds this in magnitude (default 0.02: a convention, "
                         "not a calibration -- the spread of a pair's correlation under a good fit is about 1 / sqrt(SNPs both were called at))")
-    p.add_argument("--out_name", type=str, default=None, help="name of the written files (default: --name)")
-    p.add_argument("--threads", type=int, default=1)
-    _add_extract(p)
     return p.parse_args(argv)
 
 
 def parse_cv_args(argv):
     p = argparse.ArgumentParser(prog="neural-admixture cv",
                                 description="Cross-validation error for choosing K: held-out genotype calls, from a run's .P and .Q files")
-    _add_run_heads(p)
+    _add_run_args(p, multi_k=True, out="file")
     p.add_argument("--folds", type=int, default=5, help="folds the observed calls are cut into (default 5, ADMIXTURE's)")
     _add_cv_refit(p)
     p.add_argument("--seed", type=int, default=42, help="seed of the fold draw")
-    p.add_argument("--out_name", type=str, default=None, help="name of the written file (default: --name)")
-    p.add_argument("--threads", type=int, default=1)
-    _add_extract(p)
     return p.parse_args(argv)
 
 
@@ -284,6 +266,33 @@ def _check_boot_refit(B, args, flag):
         raise SystemExit("    --boot_tol must be >= 0.")
     if args.seed < 0:
         raise SystemExit("    --seed must be >= 0.")
+
+
+def _check_polish(rounds, args, flag):
+    if rounds < 0:
+        raise SystemExit(f"    {flag} takes a number of rounds >= 0.")
+
+
+_CHECK_VALUES = {"polish": _check_polish, "cv": _check_cv_refit, "bootstrap": _check_boot_refit}    # by train()'s keyword
+_DEST = {"boot_block": "block"}                           # train()'s keywords whose flag has another name
+
+
+def _check_after_training(args, before_gpu):
+    """The refusals of `train`'s after-training options (train.AFTER_TRAINING), in their words throughout: an option's own values,
+    then a sharded run, a supervised one and a K above 16.  ``before_gpu``: the options refused before the GPU check, like an
+    analysis mode's arguments, or those refused after it; both before any data is read."""
+    for opt in AFTER_TRAINING:
+        value, flag = getattr(args, opt.kw), "--" + opt.kw
+        if opt.cli_before_gpu != before_gpu or not value:
+            continue
+        if opt.kw in _CHECK_VALUES:
+            _CHECK_VALUES[opt.kw](value, args, flag)
+        if args.num_gpus > 1:
+            raise SystemExit(f"    {flag} is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
+        if args.pops_path:
+            raise SystemExit(f"    {flag} ignores labels: it is not available with --pops_path (supervised runs).")
+        if opt.k16 is not None and (args.k is not None or args.max_k is not None):
+            _check_ks16([args.k if args.k is not None else args.max_k], flag, opt.kw)
 
 
 def _need_gpu():
@@ -355,13 +364,19 @@ def _read_on_gpu(args, keep=None):
     return _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
 
 
+def _out_stem(args):
+    """``{save_dir}/{out_name}``, --name where no --out_name was given; makes the directory."""
+    os.makedirs(args.save_dir, exist_ok=True)
+    return os.path.join(args.save_dir, args.out_name or args.name)
+
+
 def _write_id_lists(stem, ids, keep):
     """``{stem}.in`` and ``{stem}.out``: the kept and the removed SNP IDs, one per line in the order given."""
     write_id_list(f"{stem}.in", [s for s, k in zip(ids, keep) if k])
     write_id_list(f"{stem}.out", [s for s, k in zip(ids, keep) if not k])
 
 
-def _prune_main(argv, t0):
+def _prune_main(argv):
     """``prune`` mode: {save_dir}/{name}.prune.in and .prune.out, the kept and the removed SNP IDs of the .bim, one per line in file
     order (readable by plink --extract and by --extract here)."""
     from . import ld
@@ -379,11 +394,9 @@ def _prune_main(argv, t0):
     log.info(f"    LD pruning (window {args.window}, r2 {args.r2:g}): {stats['kept']} SNPs kept, {stats['removed']} removed "
              f"({stats['seconds']:.2f} seconds; {stats['ranges']} ranges).")
     log.info("    SNP lists saved.")
-    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
-    return 0
 
 
-def _hwe_main(argv, t0):
+def _hwe_main(argv):
     """``hwe`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.hwe (``id n het_obs het_exp F Z p`` per SNP in
     file order) and {out_name}.{k}.hwe.in / .hwe.out, the kept and the removed SNP IDs (readable by --extract)."""
     from . import hwe
@@ -392,21 +405,17 @@ def _hwe_main(argv, t0):
     if not 0.0 < args.alpha <= 1.0:
         raise SystemExit("    --alpha must be in (0, 1].")
     _need_bed(args.data_path, "hwe needs the SNP IDs of a .bim file")
-    P_path = find_run_files(args.save_dir, args.name, [args.k], "P", "hwe")[0]     # before anything is read
-    Q_path = find_run_files(args.save_dir, args.name, [args.k], "Q", "hwe")[0]
-    n, _, _, ids, _ = _bed_ids(args.data_path)              # before the GPU check and before any genotype is read
+    paths = _find_run_heads(args, [args.k], "hwe")         # before anything is read
+    _, _, _, ids, _ = _bed_ids(args.data_path)              # before the GPU check and before any genotype is read
     keep = _extract_keep(args.data_path, args.extract)     # (the .P then has one row per listed SNP)
     if keep is not None:
         ids = [s for s, k in zip(ids, keep) if k]
-    Q = read_run_matrix(Q_path, args.k, n)
-    P = read_run_matrix(P_path, args.k, len(ids), "model")
-    data = _read_on_gpu(args, keep)
+    data, (P,), (Q,) = _load_run_heads(args, [args.k], paths, keep)
     res = hwe.snp_hwe(data.packed, data.M, P, Q, pimin=args.pimin)
     kept = hwe.hwe_keep(res.p, args.alpha, res.n)
-    out = args.out_name or args.name
-    os.makedirs(args.save_dir, exist_ok=True)
-    hwe.write_table(os.path.join(args.save_dir, f"{out}.{args.k}.hwe"), ids, res)
-    _write_id_lists(os.path.join(args.save_dir, f"{out}.{args.k}.hwe"), ids, kept)
+    stem = f"{_out_stem(args)}.{args.k}.hwe"
+    hwe.write_table(stem, ids, res)
+    _write_id_lists(stem, ids, kept)
     Z = res.Z.cpu().numpy()
     Z = Z[~np.isnan(Z)]
     med, sd = (float(np.median(Z)), float(np.std(Z))) if len(Z) else (float("nan"), float("nan"))
@@ -416,8 +425,6 @@ def _hwe_main(argv, t0):
     if sd > 1.2:
         log.info(f"    Warning: the standard deviation of Z is {sd:.2f}; K may be too small or the panel related.")
     log.info("    Test table and SNP lists saved.")
-    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
-    return 0
 
 
 def _ks_asked(args):
@@ -437,18 +444,23 @@ def _ks_asked(args):
     return ks
 
 
-def _read_run_heads(args, ks, mode, check_n=None):
-    """{save_dir}/{name}.{K}.P and .Q of every K + the genotypes in HBM -> (data, Ps, Qs); every file is looked for and read before
-    the GPU check, and a matrix of the wrong shape ends the run, naming its file.  ``check_n(N)``: a mode's own check of the sample
-    count, run before the GPU check where the input tells N up front (.bed), else once the genotypes are parsed."""
+def _find_run_heads(args, ks, mode):
+    """The paths of {save_dir}/{name}.{K}.P and .Q of every K, ``(P_paths, Q_paths)``: an input that is neither BED nor VCF, or a
+    missing file, ends the run (``mode``: who asks) before anything is read."""
     name = os.path.basename(args.data_path)
     if ".bed" not in name and ".vcf" not in name:
         raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
-    P_paths = find_run_files(args.save_dir, args.name, ks, "P", mode)               # before anything is read
-    Q_paths = find_run_files(args.save_dir, args.name, ks, "Q", mode)
-    keep = _extract_keep(args.data_path, args.extract)     # (the .P files then have one row per listed SNP)
+    return find_run_files(args.save_dir, args.name, ks, "P", mode), find_run_files(args.save_dir, args.name, ks, "Q", mode)
+
+
+def _load_run_heads(args, ks, paths, keep, check_n=None):
+    """The files of ``_find_run_heads`` + the genotypes in HBM -> (data, Ps, Qs).  Every file is read and checked before the GPU check:
+    the widths always, the row counts where the input tells N and M without reading a genotype (.bed: the .fam file and the size of
+    the .bed), else once it is parsed; a matrix of the wrong shape ends the run, naming its file.  ``keep``: what --extract selects
+    (the .P files then have one row per listed SNP).  ``check_n(N)``: a mode's own check of the sample count, as early as N is known."""
+    P_paths, Q_paths = paths
     n_known = m_known = None
-    if ".bed" in name:                                      # N and M without reading a genotype, as the kinship mode has them
+    if ".bed" in os.path.basename(args.data_path):
         n_known, m_known, _ = _bed_shape(args.data_path, need_bim=False)
         if keep is not None:
             m_known = int(keep.sum())
@@ -459,14 +471,21 @@ def _read_run_heads(args, ks, mode, check_n=None):
     data = _read_on_gpu(args, keep)
     if check_n is not None and n_known is None:
         check_n(data.N)
-    for paths, mats, rows in ((Q_paths, Qs, data.N), (P_paths, Ps, data.M)):
-        for path, a in zip(paths, mats):
+    for paths_, mats, rows in ((Q_paths, Qs, data.N), (P_paths, Ps, data.M)):
+        for path, a in zip(paths_, mats):
             if a.shape[0] != rows:
                 raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the data needs {rows} x {a.shape[1]}.")
     return data, Ps, Qs
 
 
-def _cv_main(argv, t0):
+def _read_run_heads(args, ks, mode, check_n=None):
+    """What an analysis mode over a run's files does once its own arguments are in order: the files are looked for, then --extract is
+    resolved, then ``_load_run_heads``."""
+    paths = _find_run_heads(args, ks, mode)
+    return _load_run_heads(args, ks, paths, _extract_keep(args.data_path, args.extract), check_n)
+
+
+def _cv_main(argv):
     """``cv`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> one ``CV error (K=k): x`` line per K
     in the log and {out_name}.cv (``K cv_error se n_heldout rounds`` per K)."""
     from . import cv
@@ -477,15 +496,11 @@ def _cv_main(argv, t0):
     log.info(f"    Cross-validation over held-out calls: {args.folds} folds, at most {args.cv_rounds} refit rounds per fold.")
     results = cv.cv_error(data.packed, data.M, Ps, Qs, args.folds, args.cv_rounds, args.cv_tol, args.seed)
     cv.log_results(results, log)
-    out = args.out_name or args.name
-    os.makedirs(args.save_dir, exist_ok=True)
-    cv.write_table(os.path.join(args.save_dir, f"{out}.cv"), results)
+    cv.write_table(f"{_out_stem(args)}.cv", results)
     log.info("    Cross-validation table saved.")
-    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
-    return 0
 
 
-def _bootstrap_main(argv, t0):
+def _bootstrap_main(argv):
     """``bootstrap`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.Q_se and .Q_bias
     (N x K, the .Q text format) and one ``Bootstrap SE (K=k)`` line per K in the log."""
     from . import bootstrap
@@ -498,24 +513,22 @@ def _bootstrap_main(argv, t0):
     bootstrap.log_results(results, log, args.boot_rounds)
     bootstrap.write_results(args.save_dir, args.out_name or args.name, results)
     log.info("    Standard errors and biases of Q saved.")
-    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
-    return 0
 
 
-def _check_pse_ks(ks, flag):
-    """The check `pse` and `train --p_se` share: the K list came with ``flag``."""
+def _check_ks16(ks, who, option):
+    """The check a mode and its option of `train` share (``option``: train()'s keyword): the K list came with ``who``."""
     if max(ks) > 16:
-        raise SystemExit(f"    {flag} needs every K <= 16: the K (K + 1) / 2 running sums of a SNP live in one thread's registers "
-                         f"(K = {max(ks)} was asked for).")
+        reason = next(opt.k16 for opt in AFTER_TRAINING if opt.kw == option)
+        raise SystemExit(f"    {who} needs every K <= 16: {reason} (K = {max(ks)} was asked for).")
 
 
-def _pse_main(argv, t0):
+def _pse_main(argv):
     """``pse`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.P_se (M x K, the .P text
     format, nan where no standard error is defined) and one ``P standard errors (K=k)`` line per K in the log."""
     from . import pse
     args = parse_pse_args(argv)
     ks = _ks_asked(args)
-    _check_pse_ks(ks, "pse")
+    _check_ks16(ks, "pse", "p_se")
     if not 0.0 <= args.bound < 0.5:
         raise SystemExit("    --bound must be in [0, 0.5).")
     data, Ps, Qs = _read_run_heads(args, ks, "pse")
@@ -524,25 +537,16 @@ def _pse_main(argv, t0):
     pse.log_results(results, log)
     pse.write_results(args.save_dir, args.out_name or args.name, results)
     log.info("    Standard errors of P saved.")
-    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
-    return 0
 
 
-def _check_fit_ks(ks, flag):
-    """The check `fit` and `train --fit_check` share, in the words of `pse`: the K list came with ``flag``."""
-    if max(ks) > 16:
-        raise SystemExit(f"    {flag} needs every K <= 16: a sample's Q row and a chunk's refitted frequencies live in registers and LDS "
-                         f"(K = {max(ks)} was asked for).")
-
-
-def _fit_main(argv, t0):
+def _fit_main(argv):
     """``fit`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.cor_pop (a header line of
     group names, then the G x G mean correlations of leave-one-out residuals), {out_name}.{K}.cor_sample (``mean_cor n_pairs`` per
     sample), with --matrix {out_name}.{K}.cor (S x S, the .Q text format), and the summary and warning lines per K in the log."""
     from . import fitcheck
     args = parse_fit_args(argv)
     ks = _ks_asked(args)
-    _check_fit_ks(ks, "fit")
+    _check_ks16(ks, "fit", "fit_check")
     if not args.warn >= 0.0:
         raise SystemExit("    --warn must be >= 0.")
     if args.subsample != 0 and not 2 <= args.subsample <= fitcheck.MAX_ROWS:
@@ -573,11 +577,9 @@ def _fit_main(argv, t0):
     fitcheck.log_results(results, log, args.warn)
     fitcheck.write_results(args.save_dir, args.out_name or args.name, results, matrix=args.matrix)
     log.info("    Residual correlations saved.")
-    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
-    return 0
 
 
-def _kinship_main(argv, t0):
+def _kinship_main(argv):
     """``kinship`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.kin (``i j phi n`` per related pair, 0-based
     sample indices, by i then j) and {out_name}.{k}.inbreed (one inbreeding coefficient per sample)."""
     from . import relate
@@ -586,31 +588,12 @@ def _kinship_main(argv, t0):
     _check_k_pimin(args)
     if not args.min_phi == args.min_phi:
         raise SystemExit("    --min_phi must be a number.")
-    name = os.path.basename(args.data_path)
-    if ".bed" not in name and ".vcf" not in name:
-        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
-    P_path = find_run_files(args.save_dir, args.name, [args.k], "P", "kinship")[0]  # before anything is read
-    Q_path = find_run_files(args.save_dir, args.name, [args.k], "Q", "kinship")[0]
-    keep = _extract_keep(args.data_path, args.extract)     # (the .P then has one row per listed SNP)
-    n_known = m_known = None
-    if ".bed" in name:                                      # the .fam file and the size of the .bed give N and M without reading a genotype
-        n_known, m_known, _ = _bed_shape(args.data_path, need_bim=False)
-        if keep is not None:
-            m_known = int(keep.sum())
-    # both files are read and checked before the genotypes: the widths always, the row counts where the input tells N and M up front
-    # (.bed); a VCF's are known only once it is parsed, and are checked then
-    Q = read_run_matrix(Q_path, args.k, n_known)
-    P = read_run_matrix(P_path, args.k, m_known, "model" if m_known is not None else "data")
-    data = _read_on_gpu(args, keep)
-    for path, a, rows in ((Q_path, Q, data.N), (P_path, P, data.M)):
-        if a.shape[0] != rows:
-            raise SystemExit(f"    {path} holds a {a.shape[0]} x {a.shape[1]} matrix, the data needs {rows} x {args.k}.")
+    data, (P,), (Q,) = _read_run_heads(args, [args.k], "kinship")
     i, j, phi, n, inb = relate.kinship_pairs(data.packed, data.M, P, Q, args.min_phi, pimin=args.pimin)
     phi_h = phi.cpu().numpy()
-    out = args.out_name or args.name
-    os.makedirs(args.save_dir, exist_ok=True)
-    relate.write_pairs(os.path.join(args.save_dir, f"{out}.{args.k}.kin"), i.cpu().numpy(), j.cpu().numpy(), phi_h, n.cpu().numpy())
-    savetxt(os.path.join(args.save_dir, f"{out}.{args.k}.inbreed"), inb.cpu().numpy().reshape(-1, 1))
+    stem = f"{_out_stem(args)}.{args.k}"
+    relate.write_pairs(f"{stem}.kin", i.cpu().numpy(), j.cpu().numpy(), phi_h, n.cpu().numpy())
+    savetxt(f"{stem}.inbreed", inb.cpu().numpy().reshape(-1, 1))
     log.info(f"    {len(phi_h)} pairs with a kinship coefficient >= {args.min_phi:.4f} among {data.N} samples:")
     for label, edge, count in relate.band_counts(phi_h):
         log.info(f"      {label} (>= {edge:.4f}): {count}")
@@ -619,8 +602,6 @@ def _kinship_main(argv, t0):
         log.info(f"    Warning: {close} pairs are second-degree relatives or closer; related samples bias the fit "
                  "(the model assumes unrelated samples): consider removing one sample of each pair and training again.")
     log.info("    Kinship and inbreeding coefficients saved.")
-    log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
-    return 0
 
 
 def _read(path, device=None, keep_on_device=False, keep=None):
@@ -664,21 +645,13 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
                           master, V, pops, args.min_k, args.max_k, args.n_components, parallelism=args.parallelism,
                           host_threads=args.threads, gmm=args.gmm, precision=args.precision,
                           unlabelled=None if pops is None else (args.unlabelled,), supervised_loss_weight=args.supervised_loss_weight,
-                          polish=args.polish, polish_tol=args.polish_tol, cv=args.cv, cv_rounds=args.cv_rounds, cv_tol=args.cv_tol,
-                          bootstrap=args.bootstrap, boot_block=args.block, boot_rounds=args.boot_rounds, boot_tol=args.boot_tol,
-                          p_se=args.p_se, fit_check=args.fit_check)
+                          **{kw: getattr(args, _DEST.get(kw, kw)) for kw in AFTER_KEYWORDS})
     if master:
         save_model(model, args.name, args.save_dir)
         write_outputs(Qs, args.name, K, args.min_k, args.max_k, args.save_dir, Ps)
-        if args.bootstrap > 0:
-            from .bootstrap import write_results
-            write_results(args.save_dir, args.name, model.boot_results)
-        if args.p_se:
-            from .pse import write_results as write_pse
-            write_pse(args.save_dir, args.name, model.pse_results)
-        if args.fit_check:
-            from .fitcheck import write_results as write_fit
-            write_fit(args.save_dir, args.name, model.fit_results)
+        for opt in AFTER_TRAINING:
+            if opt.writer is not None and getattr(args, opt.kw):
+                import_module("." + opt.writer, __package__).write_results(args.save_dir, args.name, model.after_results[opt.kw])
         log.info("    Q and P matrices saved." if K is not None else "    Q and P matrices saved for all K.")
         log.info("")
         log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
@@ -697,44 +670,16 @@ def main(argv=None):
          '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "fit" checks the fit sample by sample).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
-        return _ANALYSIS_MODES[mode](argv[1:], t0)
+        _ANALYSIS_MODES[mode](argv[1:])
+        log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
+        return 0
     if mode == "train":
         args = parse_train_args(argv[1:])
-        if args.cv != 0:                                    # like an analysis mode's: before the GPU check; in --polish's words
-            _check_cv_refit(args.cv, args, "--cv")
-            if args.num_gpus > 1:
-                raise SystemExit("    --cv is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
-            if args.pops_path:
-                raise SystemExit("    --cv ignores labels: it is not available with --pops_path (supervised runs).")
-        if args.bootstrap != 0:
-            _check_boot_refit(args.bootstrap, args, "--bootstrap")
-            if args.num_gpus > 1:
-                raise SystemExit("    --bootstrap is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
-            if args.pops_path:
-                raise SystemExit("    --bootstrap ignores labels: it is not available with --pops_path (supervised runs).")
-        if args.p_se:
-            if args.num_gpus > 1:
-                raise SystemExit("    --p_se is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
-            if args.pops_path:
-                raise SystemExit("    --p_se ignores labels: it is not available with --pops_path (supervised runs).")
-            if args.k is not None or args.max_k is not None:
-                _check_pse_ks([args.k if args.k is not None else args.max_k], "--p_se")
-        if args.fit_check:
-            if args.num_gpus > 1:
-                raise SystemExit("    --fit_check is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
-            if args.pops_path:
-                raise SystemExit("    --fit_check ignores labels: it is not available with --pops_path (supervised runs).")
-            if args.k is not None or args.max_k is not None:
-                _check_fit_ks([args.k if args.k is not None else args.max_k], "--fit_check")
+        _check_after_training(args, before_gpu=True)
     _need_gpu()
     if mode == "train":
         assert args.epochs > 0 and args.batch_size > 0 and args.learning_rate > 0 and args.hidden_size > 0 and args.n_components > 0
-        if args.polish < 0:
-            raise SystemExit("    --polish takes a number of rounds >= 0.")
-        if args.polish > 0 and args.num_gpus > 1:           # before any data is read
-            raise SystemExit("    --polish is single-GPU: run it with --num_gpus 1 (a sharded run holds a part of the samples or of P).")
-        if args.polish > 0 and args.pops_path:
-            raise SystemExit("    --polish ignores labels: it is not available with --pops_path (supervised runs).")
+        _check_after_training(args, before_gpu=False)
         pops = None
         if args.pops_path:                                  # src/utils.py:28-33: one population name per line
             with open(args.pops_path, "r") as fb:

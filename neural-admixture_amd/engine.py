@@ -558,9 +558,9 @@ class Engine:
         self.pflat[L.off_v + L.p_off[h]: L.off_v + L.p_off[h] + L.M * L.kp[h]].view(L.M, L.kp[h])[:, : L.ks[h]].copy_(Pt.to(self.device))
         self.invalidate_q()                              # (P was edited: the loss path clamps until the next restrict_P)
 
-    def _analysis(self, what: str, advice: str, resident: bool = True, head: Optional[int] = None) -> None:
+    def _analysis(self, what: str, advice: str, resident: bool = True, head: Optional[int] = None, max_k=None) -> None:
         """The refusals the analysis methods below share: a sharded engine (``advice``: what to do instead), no plan or -- where the
-        method reads it whole (``resident``) -- no packed matrix, a ``head`` the model does not have."""
+        method reads it whole (``resident``) -- no packed matrix, a ``head`` the model does not have or wider than ``max_k``'s (limit, text)."""
         if self.mode != "single" or self.world != 1:
             raise NotImplementedError(f"Engine.{what} is single-GPU: a sharded engine ('dp' / 'snp') holds a part of the samples or of "
                                       f"P; {advice} instead")
@@ -568,6 +568,14 @@ class Engine:
             raise RuntimeError(f"Engine.{what} needs the HIP engine{' with its packed matrix resident' if resident else ''} (no CPU fallback)")
         if head is not None and not 0 <= head < len(self.lay.ks):
             raise RuntimeError(f"Engine.{what}: head must be in 0..{len(self.lay.ks) - 1}")
+        if max_k is not None and self.lay.ks[head] > max_k[0]:
+            raise RuntimeError(f"Engine.{what}: {max_k[1]}")
+
+    def _fitted(self, head: Optional[int] = None):
+        """What the analysis methods below start from, the engine's own fit of the resident matrix: every head's ``(Ps, Qs)``, or head
+        ``head``'s ``(P, Q)`` -- views of the P heads as they are, and the encoder's final Q."""
+        Ps, Qs = [self.P(h) for h in range(len(self.lay.ks))], final_q(self, int(self.xp.shape[0]), self.bmax)
+        return (Ps, Qs) if head is None else (Ps[head], Qs[head])
 
     def project_q(self, idx: torch.Tensor, b: int, q0: Optional[Sequence[torch.Tensor]] = None, iters: int = 20, tol: float = 1e-4,
                   with_loglik: bool = False):
@@ -598,7 +606,7 @@ class Engine:
         optimiser state are left as they are (the encoder was trained against its own P)."""
         from . import project
         self._analysis("polish", "polish with project.polish on one GPU from the written .P and .Q files")
-        return project.polish(self.xp, self.M, [self.P(h) for h in range(len(self.lay.ks))], final_q(self, int(self.xp.shape[0]), self.bmax), rounds, tol)
+        return project.polish(self.xp, self.M, *self._fitted(), rounds, tol)
 
     def cv_error(self, folds: int = 5, rounds: int = 50, tol: float = 1e-5, seed: int = 0):
         """Cross-validation error of every head over held-out CALLS of the resident matrix (cv.cv_error; include/nadm.h,
@@ -607,8 +615,7 @@ class Engine:
         parameters and optimiser state are left as they are."""
         from . import cv
         self._analysis("cv_error", "use cv.cv_error on one GPU from the written .P and .Q files")
-        return cv.cv_error(self.xp, self.M, [self.P(h) for h in range(len(self.lay.ks))], final_q(self, int(self.xp.shape[0]), self.bmax),
-                           folds, rounds, tol, seed)
+        return cv.cv_error(self.xp, self.M, *self._fitted(), folds, rounds, tol, seed)
 
     def bootstrap_q(self, B: int = 200, block: int = 1, rounds: int = 50, tol: float = 1e-5, seed: int = 0):
         """Bootstrap standard errors of every head's Q on the resident matrix (bootstrap.bootstrap_q; include/nadm.h,
@@ -617,8 +624,7 @@ class Engine:
         optimiser state are left as they are."""
         from . import bootstrap
         self._analysis("bootstrap_q", "use bootstrap.bootstrap_q on one GPU from the written .P and .Q files")
-        return bootstrap.bootstrap_q(self.xp, self.M, [self.P(h) for h in range(len(self.lay.ks))],
-                                     final_q(self, int(self.xp.shape[0]), self.bmax), B, block, rounds, tol, seed)
+        return bootstrap.bootstrap_q(self.xp, self.M, *self._fitted(), B, block, rounds, tol, seed)
 
     def kinship(self, head: int = 0, min_phi: Optional[float] = None, pimin: float = 0.0):
         """Admixture-aware kinship (REAP) of the resident matrix's samples from head ``head``'s P and the encoder's final Q
@@ -627,8 +633,7 @@ class Engine:
         assumption that the samples are unrelated; the engine's parameters and optimiser state are left as they are."""
         from . import relate
         self._analysis("kinship", "use relate.kinship_pairs on one GPU from the written .P and .Q files", head=head)
-        return relate.kinship_pairs(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], relate.MIN_PHI if min_phi is None else min_phi,
-                                    pimin=pimin)
+        return relate.kinship_pairs(self.xp, self.M, *self._fitted(head), relate.MIN_PHI if min_phi is None else min_phi, pimin=pimin)
 
     def snp_hwe(self, head: int = 0, pimin: float = 0.0):
         """Hardy-Weinberg proportions given ancestry, per SNP of the resident matrix, from head ``head``'s P and the encoder's final
@@ -637,7 +642,7 @@ class Engine:
         left as they are."""
         from . import hwe
         self._analysis("snp_hwe", "use hwe.snp_hwe on one GPU from the written .P and .Q files", head=head)
-        return hwe.snp_hwe(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], pimin=pimin)
+        return hwe.snp_hwe(self.xp, self.M, *self._fitted(head), pimin=pimin)
 
     def p_se(self, head: int = 0, bound: float = 1e-4):
         """Standard errors of head ``head``'s P, per SNP and component of the resident matrix, from the Fisher information given the
@@ -646,10 +651,8 @@ class Engine:
         ``fixed`` / ``unseen`` patterns.  Conditional on Q; K <= 16.  The engine's parameters and optimiser state are left as they
         are."""
         from . import pse
-        self._analysis("p_se", "use pse.p_se on one GPU from the written .P and .Q files", head=head)
-        if self.lay.ks[head] > pse.MAX_K:
-            raise RuntimeError(f"Engine.p_se: {pse.TOO_WIDE}")
-        return pse.p_se(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], bound=bound)
+        self._analysis("p_se", "use pse.p_se on one GPU from the written .P and .Q files", head=head, max_k=(pse.MAX_K, pse.TOO_WIDE))
+        return pse.p_se(self.xp, self.M, *self._fitted(head), bound=bound)
 
     def resid_cor(self, head: int = 0, pairs_idx=None, rows: int = 1024):
         """Model fit along the sample axis: the symmetrised correlation of leave-one-out residuals of the resident matrix's samples
@@ -657,11 +660,9 @@ class Engine:
         ``(cor float64 [S, S]`` with a NaN diagonal, ``n int32 [S, S])`` for the samples ``pairs_idx`` (default: all of them).  0 for
         every pair under a good fit; K <= 16.  The engine's parameters and optimiser state are left as they are."""
         from . import fitcheck
-        self._analysis("resid_cor", "use fitcheck.resid_cor on one GPU from the written .P and .Q files", head=head)
-        if self.lay.ks[head] > fitcheck.MAX_K:
-            raise RuntimeError(f"Engine.resid_cor: {fitcheck.TOO_WIDE}")
-        return fitcheck.resid_cor(self.xp, self.M, self.P(head), final_q(self, int(self.xp.shape[0]), self.bmax)[head], pairs_idx=pairs_idx,
-                                  rows=rows)
+        self._analysis("resid_cor", "use fitcheck.resid_cor on one GPU from the written .P and .Q files", head=head,
+                       max_k=(fitcheck.MAX_K, fitcheck.TOO_WIDE))
+        return fitcheck.resid_cor(self.xp, self.M, *self._fitted(head), pairs_idx=pairs_idx, rows=rows)
 
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""

@@ -45,9 +45,7 @@ class Q_P:
         self.ks_list = [int(k) for k in ks_list]
         self.engine = engine
         self.full_params = full_params       # SNP-sharded runs: {"V": [M,C], "P": [[M,k] ...]} gathered on the master
-        self.boot_results: Optional[list] = None   # train(..., bootstrap=B) leaves one bootstrap.BootResult per head here
-        self.pse_results: Optional[list] = None    # train(..., p_se=True) leaves one pse.PseResult per head here
-        self.fit_results: Optional[list] = None    # train(..., fit_check=True) leaves one fitcheck.FitResult per head here
+        self.after_results: dict = {}        # train(..., bootstrap / p_se / fit_check) leaves one result per head here, under the keyword
         self._pending = None
         if engine is None and V is not None:
             self._pending = {"V": V}

@@ -7,7 +7,8 @@ from __future__ import annotations
 import contextlib
 import logging
 import sys
-from typing import Optional
+from types import SimpleNamespace
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -219,6 +220,47 @@ def capped_host_threads(limit: int = 4):
         torch.set_num_threads(prev)
 
 
+class AfterOption(NamedTuple):
+    """An option of train() that runs after training.  train(), the CLI's ``train`` mode and tests/test_after_training.py read these
+    records: a new option is a record, its keywords in train()'s signature and docstring, and its block at the end of _train."""
+    kw: str                          # train()'s keyword that switches it on (> 0 or True); the CLI flag is "--" + kw
+    params: Tuple[str, ...]          # every keyword of train() that belongs to it, ``kw`` first
+    check: Optional[Callable]        # its own value checks: check(after) raises ValueError
+    k16: Optional[str]               # needs every K <= 16: the reason the CLI gives; None: any K
+    writer: Optional[str]            # the module whose write_results(save_dir, name, results) writes model.after_results[kw]
+    cli_before_gpu: bool = True      # the CLI refuses before its GPU check (--polish, the oldest, after it)
+
+
+def _check_polish(o):
+    if o.polish < 0:
+        raise ValueError("polish must be >= 0 rounds")
+
+
+def _check_cv(o):
+    if o.cv != 0 and not 2 <= o.cv <= 64:
+        raise ValueError("cv must be 0 or a number of folds in 2..64")
+    if o.cv > 0 and o.cv_rounds < 1:
+        raise ValueError("cv_rounds must be >= 1")
+
+
+def _check_bootstrap(o):
+    if o.bootstrap != 0 and o.bootstrap < 2:
+        raise ValueError("bootstrap must be 0 or a number of replicates >= 2")
+    if o.bootstrap > 0 and (o.boot_rounds < 1 or o.boot_block < 1):
+        raise ValueError("boot_rounds and boot_block must be >= 1")
+
+
+AFTER_TRAINING = (                                        # in the order they run
+    AfterOption("polish", ("polish", "polish_tol"), _check_polish, None, None, cli_before_gpu=False),
+    AfterOption("cv", ("cv", "cv_rounds", "cv_tol"), _check_cv, None, None),
+    AfterOption("bootstrap", ("bootstrap", "boot_block", "boot_rounds", "boot_tol"), _check_bootstrap, None, "bootstrap"),
+    AfterOption("p_se", ("p_se",), None, "the K (K + 1) / 2 running sums of a SNP live in one thread's registers", "pse"),
+    AfterOption("fit_check", ("fit_check",), None, "a sample's Q row and a chunk's refitted frequencies live in registers and LDS",
+                "fitcheck"),
+)
+AFTER_KEYWORDS = tuple(p for opt in AFTER_TRAINING for p in opt.params)
+
+
 def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
           num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
           n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto", precision: str = "highest",
@@ -236,72 +278,54 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
     like any other and stay out of the supervised term and of the class means of the decoder init (supervised_init).
     ``supervised_loss_weight`` (keyword, CLI --supervised_loss_weight): the weight of the supervised term, 100 like the reference's
     default.
-    ``polish`` / ``polish_tol`` (keyword, CLI --polish / --polish_tol): after training, up to ``polish`` rounds of block EM over the
-    OBSERVED calls (Engine.polish) started from the trained P and the encoder's Q; the returned ``Ps`` and ``Qs`` are then the
-    polished ones -- training reads a missing call as genotype 0, which pulls P down wherever calls are missing -- while the
-    returned model stays as trained.  Single-GPU, unsupervised runs only; 0 (the default) calls nothing.
-    ``cv`` / ``cv_rounds`` / ``cv_tol`` (keyword, CLI --cv / --cv_rounds / --cv_tol): after training -- and after polishing, where
-    ``polish`` is given -- the cross-validation error of every K over ``cv`` folds of held-out CALLS (cv.cv_error, fold seed
-    ``seed``), refitted from the matrices about to be returned, is logged as ``CV error (K=k): x``.  Single-GPU, unsupervised runs
-    only; 0 (the default) calls nothing.
+    The options that run after training (AFTER_TRAINING), in this order, each on the matrices about to be returned: single-GPU,
+    unsupervised runs only; 0 or False (the defaults) call nothing; what has a file format is logged and left in the returned model's
+    ``after_results`` under the option's keyword (absent without it), from where the CLI writes it.
+    ``polish`` / ``polish_tol`` (keyword, CLI --polish / --polish_tol): up to ``polish`` rounds of block EM over the OBSERVED calls
+    (Engine.polish) started from the trained P and the encoder's Q; the returned ``Ps`` and ``Qs`` are then the polished ones --
+    training reads a missing call as genotype 0, which pulls P down wherever calls are missing -- while the returned model stays as
+    trained.
+    ``cv`` / ``cv_rounds`` / ``cv_tol`` (keyword, CLI --cv / --cv_rounds / --cv_tol): the cross-validation error of every K over
+    ``cv`` folds of held-out CALLS (cv.cv_error, fold seed ``seed``), refitted from those matrices, is logged as
+    ``CV error (K=k): x``.
     ``bootstrap`` / ``boot_block`` / ``boot_rounds`` / ``boot_tol`` (keyword, CLI --bootstrap / --block / --boot_rounds / --boot_tol):
-    after all of the above, bootstrap standard errors of every K's Q from ``bootstrap`` replicates that resample the SNPs in blocks
-    of ``boot_block`` (bootstrap.bootstrap_q, draw seed ``seed``), refitted from the matrices about to be returned; logged, and left
-    in the returned model's ``boot_results`` (None without it; the CLI writes them as .Q_se / .Q_bias).  Single-GPU, unsupervised
-    runs only; 0 (the default) calls nothing.
-    ``p_se`` (keyword, CLI --p_se): after all of the above, the standard errors of every K's P from the per-SNP Fisher information
-    given the Q about to be returned (pse.p_se; every K <= 16); logged, and left in the returned model's ``pse_results`` (None
-    without it; the CLI writes them as .P_se).  Single-GPU, unsupervised runs only; False (the default) calls nothing.
-    ``fit_check`` (keyword, CLI --fit_check): after all of the above, the model-fit check of every K from the matrices about to be
-    returned (fitcheck.fit_check: the correlation of leave-one-out residuals, grouped by largest component; every K <= 16; above
-    4096 samples the pairs of a subset drawn with ``seed``); logged, and left in the returned model's ``fit_results`` (None without
-    it; the CLI writes them as .cor_pop / .cor_sample).  Single-GPU, unsupervised runs only; False (the default) calls nothing."""
+    bootstrap standard errors of every K's Q from ``bootstrap`` replicates that resample the SNPs in blocks of ``boot_block``
+    (bootstrap.bootstrap_q, draw seed ``seed``), refitted from those matrices (files: .Q_se / .Q_bias).
+    ``p_se`` (keyword, CLI --p_se): the standard errors of every K's P from the per-SNP Fisher information given the Q about to be
+    returned (pse.p_se; every K <= 16; file: .P_se).
+    ``fit_check`` (keyword, CLI --fit_check): the model-fit check of every K (fitcheck.fit_check: the correlation of leave-one-out
+    residuals, grouped by largest component; every K <= 16; above 4096 samples the pairs of a subset drawn with ``seed``; files:
+    .cor_pop / .cor_sample)."""
+    after = SimpleNamespace(**{name: value for name, value in locals().items() if name in AFTER_KEYWORDS})   # (first: only arguments yet)
     if precision not in PRECISIONS:
         raise ValueError("precision must be 'highest' or 'medium'")
-    if polish < 0:
-        raise ValueError("polish must be >= 0 rounds")
-    if polish > 0 and (num_gpus > 1 or pops is not None):
-        raise ValueError("polish needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
-    if cv != 0 and not 2 <= cv <= 64:
-        raise ValueError("cv must be 0 or a number of folds in 2..64")
-    if cv > 0 and cv_rounds < 1:
-        raise ValueError("cv_rounds must be >= 1")
-    if cv > 0 and (num_gpus > 1 or pops is not None):
-        raise ValueError("cv needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
-    if bootstrap != 0 and bootstrap < 2:
-        raise ValueError("bootstrap must be 0 or a number of replicates >= 2")
-    if bootstrap > 0 and (boot_rounds < 1 or boot_block < 1):
-        raise ValueError("boot_rounds and boot_block must be >= 1")
-    if bootstrap > 0 and (num_gpus > 1 or pops is not None):
-        raise ValueError("bootstrap needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
-    if p_se and (num_gpus > 1 or pops is not None):
-        raise ValueError("p_se needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
-    if p_se and max([k for k in ((K,) if K is not None else (max_k,)) if k is not None], default=0) > 16:
-        raise ValueError("p_se needs every K <= 16")
-    if fit_check and (num_gpus > 1 or pops is not None):
-        raise ValueError("fit_check needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
-    if fit_check and max([k for k in ((K,) if K is not None else (max_k,)) if k is not None], default=0) > 16:
-        raise ValueError("fit_check needs every K <= 16")
+    k_max = K if K is not None else (max_k or 0)           # the largest K asked for
+    for opt in AFTER_TRAINING:
+        if opt.check is not None:
+            opt.check(after)
+        if not getattr(after, opt.kw) > 0:
+            continue
+        if num_gpus > 1 or pops is not None:
+            raise ValueError(f"{opt.kw} needs a single-GPU, unsupervised run (it ignores labels and works on the whole resident matrix)")
+        if opt.k16 is not None and k_max > 16:
+            raise ValueError(f"{opt.kw} needs every K <= 16")
     with capped_host_threads(max(1, int(host_threads))):
         return _train(epochs, batch_size, learning_rate, K, seed, data, device, num_gpus, hidden_size, master, V, pops, min_k, max_k,
                       n_components, parallelism=parallelism, gmm=gmm, precision=precision, unlabelled=unlabelled,
-                      supervised_loss_weight=supervised_loss_weight, polish=polish, polish_tol=polish_tol, cv=cv, cv_rounds=cv_rounds,
-                      cv_tol=cv_tol, bootstrap=bootstrap, boot_block=boot_block, boot_rounds=boot_rounds, boot_tol=boot_tol, p_se=p_se,
-                      fit_check=fit_check)
+                      supervised_loss_weight=supervised_loss_weight, after=after)
 
 
 def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int, data: torch.Tensor, device: torch.device,
            num_gpus: int, hidden_size: int, master: bool, V: np.ndarray, pops, min_k: int = None, max_k: int = None,
            n_components: int = None, *, parallelism: str = "dp", gmm: str = "auto", precision: str = "highest", unlabelled=None,
-           supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5, cv: int = 0, cv_rounds: int = 50,
-           cv_tol: float = 1e-5, bootstrap: int = 0, boot_block: int = 1, boot_rounds: int = 50, boot_tol: float = 1e-5, p_se: bool = False,
-           fit_check: bool = False):
+           supervised_loss_weight: float = 100.0, after: SimpleNamespace):
     """See module docstring.  ``data`` uint8 [N,M] CPU tensor (or an ``io.PackedGenotypes``, e.g. from
     ``io.read_bed_packed``); ``V`` numpy [C,M] (RSVD output,
     svd.py:83); returns Ps (list of [M,k] float32), Qs (list of [N,k] float32), model.
     ``parallelism`` (keyword, not in the reference): "dp" = samples sharded over the GPUs, gradients summed over ranks like the reference's DDP (here: reduce-scatter,
     optimizer on the rank's slice, all-gather); "snp" = SNPs sharded (snp_parallel.py): same trajectory up to summation order, two tiny all-reduces
-    per step instead of the 4*M*(C+S)-byte one."""
+    per step instead of the 4*M*(C+S)-byte one.
+    ``after``: train()'s after-training keywords (AFTER_TRAINING), already checked."""
     eng_cls = NeuralAdmixture.engine_snp_cls if parallelism == "snp" else NeuralAdmixture.engine_cls
     if not eng_cls.supports(device):
         raise RuntimeError("neural_admixture_amd.train requires a ROCm GPU device; the CPU path is the reference's own")
@@ -357,33 +381,34 @@ def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int
                             supervised_loss_weight=supervised_loss_weight, parallelism=parallelism, precision=precision)
     Qs, Ps, raw = model.launch_training(P_init, data, hidden_size, Vt.shape[1], Vt, M, N, pops)
 
-    if polish > 0:                                         # (the log-likelihood below is then that of the polished matrices)
-        Pp, Qp, ll0, ll1, ran = model.engine.polish(polish, polish_tol)
+    if after.polish > 0:                                   # (the log-likelihood below is then that of the polished matrices)
+        Pp, Qp, ll0, ll1, ran = model.engine.polish(after.polish, after.polish_tol)
         Ps, Qs = [x.cpu().numpy() for x in Pp], [x.cpu().numpy() for x in Qp]
         log.info(f"    Log-likelihood of the observed calls before polishing: {ll0:.3f}")
         log.info(f"    Log-likelihood of the observed calls after polishing:  {ll1:.3f}")
         log.info(f"    Polishing rounds run: {ran}")
         log.info("")
-    if cv > 0:                                             # on the matrices about to be returned
+    xp, done = model.engine.xp, raw.after_results          # what is logged below and has a writer goes there under its keyword
+    if after.cv > 0:                                       # on the matrices about to be returned
         from . import cv as _cv
-        _cv.log_results(_cv.cv_error(model.engine.xp, M, Ps, Qs, cv, cv_rounds, cv_tol, seed), log)
+        _cv.log_results(_cv.cv_error(xp, M, Ps, Qs, after.cv, after.cv_rounds, after.cv_tol, seed), log)
         log.info("")
-    if bootstrap > 0:                                      # likewise; the written .Q stays the one above, the centre goes with the results
+    if after.bootstrap > 0:                                # likewise; the written .Q stays the one above, the centre goes with the results
         from . import bootstrap as _boot
-        raw.boot_results = _boot.bootstrap_q(model.engine.xp, M, Ps, Qs, bootstrap, boot_block, boot_rounds, boot_tol, seed)
-        _boot.log_results(raw.boot_results, log, boot_rounds)
+        done["bootstrap"] = _boot.bootstrap_q(xp, M, Ps, Qs, after.bootstrap, after.boot_block, after.boot_rounds, after.boot_tol, seed)
+        _boot.log_results(done["bootstrap"], log, after.boot_rounds)
         log.info("")
-    if p_se:                                               # likewise: of the P about to be returned, given the Q about to be returned
+    if after.p_se:                                         # likewise: of the P about to be returned, given the Q about to be returned
         from . import pse as _pse
-        raw.pse_results = [_pse.p_se(model.engine.xp, M, P_k, Q_k) for P_k, Q_k in zip(Ps, Qs)]
-        _pse.log_results(raw.pse_results, log)
+        done["p_se"] = [_pse.p_se(xp, M, P_k, Q_k) for P_k, Q_k in zip(Ps, Qs)]
+        _pse.log_results(done["p_se"], log)
         log.info("")
-    if fit_check:                                          # likewise: of the P and Q about to be returned
+    if after.fit_check:                                    # likewise: of the P and Q about to be returned
         from . import fitcheck as _fit
-        n_all = int(model.engine.xp.shape[0])
+        n_all = int(xp.shape[0])
         pairs = None if n_all <= _fit.MAX_ROWS else np.sort(np.random.default_rng(seed).choice(n_all, size=_fit.MAX_ROWS, replace=False))
-        raw.fit_results = [_fit.fit_check(model.engine.xp, M, P_k, Q_k, None, pairs) for P_k, Q_k in zip(Ps, Qs)]
-        _fit.log_results(raw.fit_results, log)
+        done["fit_check"] = [_fit.fit_check(xp, M, P_k, Q_k, None, pairs) for P_k, Q_k in zip(Ps, Qs)]
+        _fit.log_results(done["fit_check"], log)
         log.info("")
     if master:
         ks = [K] if K is not None else list(range(min_k, max_k + 1))

@@ -26,9 +26,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hwe_oracle as HO  # noqa: E402
 import ld_oracle as LO  # noqa: E402
-from packed_rows import dev as _dev, packed as _packed  # noqa: E402
+from packed_rows import case_rows, dev as _dev, packed as _packed  # noqa: E402
 
 ROWS = 200                   # resident rows of the GPU cases
+_rows = functools.partial(case_rows, resident=ROWS)
 # (b, M, K, pimin, rows): every b, M, K and pimin of the issue at least once, not their product.  rows: "list" = a permuted gather
 # list with a duplicate, "none" = rows 0..b without a list
 CASES = [(1, 257, 2, 0.0, "list"), (70, 1027, 3, 0.05, "none"), (130, 3001, 8, 0.0, "list"), (200, 257, 9, 0.05, "list"),
@@ -57,24 +58,6 @@ def _case(M, K):
 def _terms(M, K, pimin):
     Gm, P, Q, _ = _case(M, K)
     return HO.terms(Gm, P, Q, pimin)
-
-
-def _rows(b, kind="list"):
-    """The rows of a case: "none" = 0..b; "list" = a permutation of the resident rows with the one-hot row 2, the all-missing row 4
-    and the 7-call row 5 in it, cut to b, the last entry a duplicate of the first (b = 1: row 7); b > ROWS: drawn with repeats, the
-    planted rows among them."""
-    if kind == "none":
-        return np.arange(b, dtype=np.int32)
-    if b == 1:
-        return np.asarray([7], dtype=np.int32)
-    if b > ROWS:
-        idx = np.random.default_rng(b).integers(0, ROWS, size=b).astype(np.int32)
-        idx[[3, b // 2, b - 2]] = [2, 4, 5]
-        return idx
-    perm = np.random.default_rng(100 * b).permutation(ROWS)
-    perm = np.concatenate([[2, 4, 5], perm[(perm != 2) & (perm != 4) & (perm != 5)]])[:b - 1]
-    perm = perm[np.random.default_rng(100 * b + 1).permutation(b - 1)]
-    return np.concatenate([perm, perm[:1]]).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=None)

@@ -29,9 +29,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hwe_oracle as HO  # noqa: E402
 import ld_oracle as LO  # noqa: E402
 import pse_oracle as PO  # noqa: E402
-from packed_rows import dev as _dev, packed as _packed  # noqa: E402
+from packed_rows import case_rows, dev as _dev, packed as _packed  # noqa: E402
 
 ROWS = 200                   # resident rows of the GPU cases
+_rows = functools.partial(case_rows, resident=ROWS)
 # (b, M, K, rows): every b, M and K of the issue at least once, not their product: every kp (4, 8, 12, 16) full and with a K below it.
 # rows: "list" = a permuted gather list with a duplicate, "none" = rows 0..b without a list
 CASES = [(1, 257, 2, "list"), (70, 1027, 3, "none"), (130, 3001, 8, "list"), (200, 257, 9, "list"), (70, 3001, 16, "list"),
@@ -56,24 +57,6 @@ def _case(M, K):
 def _weights(M, K):
     Gm, P, Q, _ = _case(M, K)
     return PO.weights(Gm, P, Q)
-
-
-def _rows(b, kind="list"):
-    """The rows of a case: "none" = 0..b; "list" = a permutation of the resident rows with the one-hot row 2, the all-missing row 4
-    and the 7-call row 5 in it, cut to b, the last entry a duplicate of the first (b = 1: row 7); b > ROWS: drawn with repeats, the
-    planted rows among them."""
-    if kind == "none":
-        return np.arange(b, dtype=np.int32)
-    if b == 1:
-        return np.asarray([7], dtype=np.int32)
-    if b > ROWS:
-        idx = np.random.default_rng(b).integers(0, ROWS, size=b).astype(np.int32)
-        idx[[3, b // 2, b - 2]] = [2, 4, 5]
-        return idx
-    perm = np.random.default_rng(100 * b).permutation(ROWS)
-    perm = np.concatenate([[2, 4, 5], perm[(perm != 2) & (perm != 4) & (perm != 5)]])[:b - 1]
-    perm = perm[np.random.default_rng(100 * b + 1).permutation(b - 1)]
-    return np.concatenate([perm, perm[:1]]).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=None)

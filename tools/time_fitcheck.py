@@ -13,6 +13,7 @@ Admixture-model genotypes from nadm_synth_packed, 2 % missing; device events, th
 """
 import argparse
 import ctypes as C
+import functools
 import sys
 
 import numpy as np
@@ -20,8 +21,8 @@ import torch
 
 sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 from neural_admixture_amd._lib import lib, check, ptr  # noqa: E402
-from neural_admixture_amd.layout import ModelLayout  # noqa: E402
 from neural_admixture_amd import fitcheck  # noqa: E402
+from _timing import synth_model, timed  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=5)
@@ -36,30 +37,8 @@ assert torch.cuda.is_available(), "time_fitcheck.py measures on the GPU; there i
 dev = torch.device("cuda:0")
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 rng = np.random.default_rng(1)
+synth = functools.partial(synth_model, rng=rng, dev=dev, st=st)
 EPS = 1e-6
-
-
-def synth(rows, M, K):
-    """(xp [rows, ld], P [M, kp], Q [rows, kp], kp, ld): genotypes drawn from the model (P, Q), 2 % missing."""
-    kp, ld = int(lib.nadm_pad_k(K)), ModelLayout.row_stride(M)
-    Fq = torch.from_numpy(np.clip(0.5 * rng.beta(0.5, 0.5, size=(K, M)), 0.005, 0.5).astype(np.float32)).to(dev)
-    Qt = torch.from_numpy(rng.dirichlet(0.2 * np.ones(K), size=rows).astype(np.float32)).to(dev)
-    xp = torch.zeros((rows, ld), dtype=torch.uint8, device=dev)
-    check(lib.nadm_synth_packed(ptr(xp), rows, 0, M, ld, ptr(Qt), ptr(Fq), K, 0.02, 7, st), "synth_packed")
-    P = torch.zeros((M, kp), dtype=torch.float32, device=dev)
-    P[:, :K] = Fq.T
-    Q = torch.zeros((rows, kp), dtype=torch.float32, device=dev)
-    Q[:, :K] = Qt
-    return xp, P, Q, kp, ld
-
-
-def timed(f):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    f()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
 
 
 def quart(v):
