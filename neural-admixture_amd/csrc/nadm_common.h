@@ -45,6 +45,62 @@ __device__ __forceinline__ uint32_t obs_mask(uint32_t code) {
     return m;
 }
 
+// ---- sample slices of the sliced passes 2 and 3: ONE rule for the kernels and for the host code that chooses and checks n_slices ----------
+// Slice s walks tiles [s tps, min(tiles, s tps + tps)), tps = ceil(tiles / n_slices).  The host refuses a count that leaves the last slice
+// empty: it would never be counted and the hand-off below would never complete.
+struct TileRange { int lo, hi; };
+__host__ __device__ constexpr int slice_tps(int tiles, int n_slices) { return (tiles + n_slices - 1) / n_slices; }
+__host__ __device__ constexpr TileRange slice_tiles(int tiles, int n_slices, int slice) {
+    const int tps = slice_tps(tiles, n_slices), lo = slice * tps;
+    return TileRange{lo, tiles < lo + tps ? tiles : lo + tps};
+}
+__host__ __device__ constexpr bool slices_leave_one_empty(int tiles, int n_slices) { return slice_tiles(tiles, n_slices, n_slices - 1).lo >= tiles; }
+// the largest count <= min(s, tiles) that leaves no slice empty; 1 = unsliced
+__host__ __device__ constexpr int slices_without_empty(int tiles, int s) { return s < 2 || tiles < 2 ? 1 : slice_tps(tiles, slice_tps(tiles, s < tiles ? s : tiles)); }
+
+// ---- the park-and-count hand-off between blocks of one launch ---------------------------------------------------------------------------
+// Users: the sliced pass 2 (decode_bce_bf16_kernel: a chunk's dP and loss partials), the sliced pass 3 (encode_bwd_fp4_kernel: the dV
+// partials) and the MLP backward that builds pass 3's dZ image (mlp_bwd_a kernels: the dZ rows of a 32-sample group).  A block parks its
+// payload, is counted, and the block counted LAST reads every payload back, possibly on another XCD with an L2 of its own; nobody waits and
+// there is no fence (a __threadfence writes back the XCD's whole L2: +20 us in the MLP backward).  The C++ memory model calls the sequence
+// a data race (relaxed atomics); what orders it is what the INSTRUCTIONS do on gfx950, which is why a test pins them in every user
+// (tests/test_abi_and_host.py, test_dz_image_hand_off_compiles_to_the_instructions_its_contract_names, from hipcc -S):
+//  1. the payload is stored with `global_store_dword ... sc1` (an agent-scope atomic store): the XCD's L2 writes it THROUGH and keeps no
+//     dirty line (sc1 stores drop the line) -- there is nothing a later write-back could deliver late;
+//  2. `s_waitcnt vmcnt(0)` in every wave, then `s_barrier`: on gfx9 stores count in vmcnt, which falls when the write is acknowledged at
+//     the scope the instruction names -- device scope for sc1 -- so every wave's payload is at the device's point of coherence before
+//     the block is counted;
+//  3. one lane counts the block with `global_atomic_add ... sc0` -- a returning device-scope read-modify-write performed at that same
+//     point of coherence, so blocks of different XCDs see one counter; the value it returns tells the last arrival that the others'
+//     step 2 happened before;
+//  4. the last block reads the payloads with `global_load_dword ... sc1`: such loads bypass the CU's L1 and cannot be served by a stale
+//     line of this XCD's L2 for data the writer stored sc1 ("sc1 loads may replace the acquire only when the producer stored sc1"); the
+//     counter is returned to zero with an sc1 store for the next launch (and Engine.load_params zeroes the dZ image's counters, so an
+//     aborted launch cannot leave a group half-counted).
+// What would break it: a compiler that emitted plain stores or dropped the wait (the test), or hardware whose sc1 stores stopped writing
+// through.  The soaks are the empirical half.
+constexpr int WAITCNT_VMCNT0 = 0x0F70;       // s_waitcnt simm16 on gfx9: vmcnt (bits 3:0, 15:14) = 0, expcnt and lgkmcnt at their maxima = not waited for
+__device__ __forceinline__ void handoff_put(float* dst, float v) { __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void handoff_put4(float* dst, const float4 v) { handoff_put(dst + 0, v.x); handoff_put(dst + 1, v.y); handoff_put(dst + 2, v.z); handoff_put(dst + 3, v.w); }   // four dword stores
+__device__ __forceinline__ float handoff_get(const float* src) { return __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void handoff_add4(float4& acc, const float* p) { acc.x += handoff_get(p + 0); acc.y += handoff_get(p + 1); acc.z += handoff_get(p + 2); acc.w += handoff_get(p + 3); }   // (the last block adds the partials in index order, whoever it is)
+// every thread calls it after its last handoff_put; true (block-uniform) in the block counted as number `expected` (an int, or a callable that the counting thread alone evaluates)
+template <class Expected>
+__device__ __forceinline__ bool handoff_count_last(int* counter, Expected expected) {
+    __shared__ int s_last;
+    __builtin_amdgcn_s_waitcnt(WAITCNT_VMCNT0);                       // this wave's stores have been acknowledged ...
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int n = expected();
+        const int old = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ... before the block is counted
+        s_last = old == n - 1;
+        if (s_last) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);            // ready for the next launch
+    }
+    __syncthreads();
+    return s_last;
+}
+__device__ __forceinline__ bool handoff_count_last(int* counter, int expected) { return handoff_count_last(counter, [=] { return expected; }); }
+
 // ---- vectors of four dwords (one 16-byte load or store, one MFMA operand or accumulator) ---------
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef int i32x4_t __attribute__((ext_vector_type(4)));

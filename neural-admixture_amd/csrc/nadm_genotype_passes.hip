@@ -791,13 +791,12 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
     unsigned long long pc0 = 0, pr0 = 0;
     if (probe) { pc0 = __builtin_readcyclecounter(); pr0 = __builtin_amdgcn_s_memrealtime(); }
     // gridDim.y = S sample SLICES (r05): with few SNP chunks (M below ~130k) a launch lasts as long as one block's serial chain over all the
-    // sample tiles, not as long as the chip needs -- the batch's sample tiles are dealt to S blocks per chunk.  Everything a block writes is per sample (dQ slab rows, the batch copy) except dP and
-    // the loss value: every slice parks its partial [chunk SNPs x KP] sum (+ its loss partial) in `slab`, is counted, and the block that
-    // is counted LAST adds the S partials in slice order and runs the epilogue (Adam or the gradient store) -- the hand-off idiom of
-    // the MLP backward's dZ image (nadm_small_kernels.hip: write-through stores, vmcnt(0), device-scope counter, device-scope loads;
-    // DESIGN 4.3), no block ever waits for another.  The sum's order is fixed, so a step is reproducible bit for bit; it is NOT the
-    // S = 1 kernel's order (one accumulator over all tiles), which is why the slicing is decided inside the library from (b, M) alone
-    // (nadm_decode_slices) and every path to this kernel takes the same decision.
+    // sample tiles, not as long as the chip needs -- the batch's sample tiles are dealt to S blocks per chunk.  Everything a block writes is
+    // per sample (dQ slab rows, the batch copy) except dP and the loss value: every slice parks its partial [chunk SNPs x KP] sum (+ its loss
+    // partial) in `slab`, is counted, and the block that is counted LAST adds the S partials in slice order and runs the epilogue (Adam or the
+    // gradient store) -- the park-and-count hand-off of nadm_common.h, no block ever waits for another.  The sum's order is fixed,
+    // so a step is reproducible bit for bit; it is NOT the S = 1 kernel's order (one accumulator over all tiles), which is why the slicing is
+    // decided inside the library from (b, M) alone (nadm_decode_slices) and every path to this kernel takes the same decision.
     // W (KP 9..16): k spans two 8-wide MFMA slots.  The pieces can no longer share an MFMA's 16 rows / columns, so
     //   R^T  = [Ph Ph' Ph Ph'].[Qh Qh' Qm Qm'] + [Pm Pm' Pm Pm'].[Qh Qh' Qm Qm'] + [Ph Ph' Pl Pl'].[Ql Ql' Qh Qh']   (X' = k 8..15)
     //   dQ^T = Ph.(dRh + dRl) + Pm.dRh    rows = the 16 k, three MFMAs (per two tiles) into one accumulator, no fold
@@ -1041,13 +1040,13 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
 
     const int n_slices = SLICED ? (int)gridDim.y : 1, slice = SLICED ? (int)blockIdx.y : 0;
     const int ntiles = (b + MF_TS - 1) / MF_TS;
-    const int tps = (ntiles + n_slices - 1) / n_slices;      // (the host picks S so that no slice is empty)
-    const int tl0 = SLICED ? slice * tps : 0, tl1 = SLICED ? min(ntiles, tl0 + tps) : ntiles;
+    const TileRange mine_t = SLICED ? slice_tiles(ntiles, n_slices, slice) : TileRange{0, ntiles};     // (the host's rule too: no slice is empty)
+    const int tl0 = mine_t.lo, tl1 = mine_t.hi;
     if constexpr (SLICED) row_pref = row_index(tl0 * MF_TS);
     __syncthreads();                                        // zero fill visible before the first commit
     issue(tl0 * MF_TS);
     commit(tl0 * MF_TS);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __builtin_amdgcn_s_waitcnt(WAITCNT_VMCNT0);
     __syncthreads();
 
     float kmax_v = 1e-12f;                                 // 1 / 1e-12 as v_rcp_f32 computes it (opaque to the constant folder)
@@ -1286,40 +1285,18 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
     // ---- S > 1: park the partial, be counted, the last one adds them up (see the head of the kernel)
     constexpr int SLAB_F = p2_slab_floats(KP);                        // floats per (slice, chunk): the slab + 4 (the loss partial + pad)
     float* const mine = slab + ((int64_t)slice * gridDim.x + chunk) * SLAB_F;
-    for (int e = tid; e < CH_F4; e += NTHR) {
-        const float4 g4 = *reinterpret_cast<const float4*>(s_dp + 4 * e);
-        __hip_atomic_store(mine + 4 * e + 0, g4.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // written THROUGH to memory: the block
-        __hip_atomic_store(mine + 4 * e + 1, g4.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // that adds the partials may sit on
-        __hip_atomic_store(mine + 4 * e + 2, g4.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // another XCD, behind another L2
-        __hip_atomic_store(mine + 4 * e + 3, g4.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (tid == 0) __hip_atomic_store(mine + 4 * CH_F4, my_loss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __shared__ int s_last;
-    __builtin_amdgcn_s_waitcnt(0x0F70);                               // vmcnt(0): this wave's stores have been acknowledged ...
-    __syncthreads();
-    if (tid == 0) {
-        const int old = __hip_atomic_fetch_add(&slice_cnt[chunk], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... before the block is counted
-        s_last = old == n_slices - 1;
-        if (s_last) __hip_atomic_store(&slice_cnt[chunk], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // ready for the next launch
-    }
-    __syncthreads();
-    if (!s_last) return;                                              // block-uniform
+    for (int e = tid; e < CH_F4; e += NTHR) handoff_put4(mine + 4 * e, *reinterpret_cast<const float4*>(s_dp + 4 * e));
+    if (tid == 0) handoff_put(mine + 4 * CH_F4, my_loss);
+    if (!handoff_count_last(&slice_cnt[chunk], n_slices)) return;     // block-uniform
     for (int e = tid; e < CH_F4; e += NTHR) {
         float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int sl = 0; sl < n_slices; ++sl) {                       // slice order, whoever is last
-            const float* part = slab + ((int64_t)sl * gridDim.x + chunk) * SLAB_F + 4 * e;
-            g4.x += __hip_atomic_load(part + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g4.y += __hip_atomic_load(part + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g4.z += __hip_atomic_load(part + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g4.w += __hip_atomic_load(part + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        for (int sl = 0; sl < n_slices; ++sl) handoff_add4(g4, slab + ((int64_t)sl * gridDim.x + chunk) * SLAB_F + 4 * e);     // slice order, whoever is last
         finish(e, g4);
     }
     if constexpr (LOSS) {
         if (tid == 0) {
             float tot = 0.f;
-            for (int sl = 0; sl < n_slices; ++sl)
-                tot += __hip_atomic_load(slab + ((int64_t)sl * gridDim.x + chunk) * SLAB_F + 4 * CH_F4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int sl = 0; sl < n_slices; ++sl) tot += handoff_get(slab + ((int64_t)sl * gridDim.x + chunk) * SLAB_F + 4 * CH_F4);
             losspart[chunk] = tot;
         }
     }
@@ -1377,7 +1354,7 @@ constexpr int p3_slab_floats(int cp) { return EB_CHUNK_SNPS * cp; }
 // a rank of the SNP-sharded mode (6400 rows x 62.5k SNPs at configs[3] on 8 GPUs) launches 122 blocks on 256 CUs and runs 75 us where the
 // single-GPU shape (800 x 500k, the same genotypes) runs 41.  The tiles are dealt to S blocks per chunk; every slice parks its partial
 // [512 x CP] sum in `slab`, is counted, and the block counted LAST adds the S partials in slice order and runs the epilogue (Adam on the
-// chunk's V rows, or the gradient store) -- pass 2's idiom (decode_bce_bf16_kernel), the dZ image's hand-off contract: nobody
+// chunk's V rows, or the gradient store) -- pass 2's idiom (decode_bce_bf16_kernel), the hand-off and its contract in nadm_common.h: nobody
 // waits, the sum's order is fixed, S is a function of (b, M) alone (nadm_encode_slices).  false compiles the kernel as it stood.
 template <int CP, bool CLEAN_SRC, bool SLICED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void encode_bwd_fp4_kernel(const uint8_t* __restrict__ xp, int64_t ld,
@@ -1481,8 +1458,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // (~1.5 k cycles of work per wave) before they are committed, its row indices one phase before that.
     const int ntiles_all = (b + DZI_TS - 1) / DZI_TS;
     const int slice = SLICED ? (int)(blockIdx.x / nchunks) : 0;
-    const int tps = (ntiles_all + n_slices - 1) / n_slices;       // (the host picks S so that no slice is empty)
-    const int tl0 = SLICED ? slice * tps : 0, ntiles = SLICED ? min(ntiles_all, tl0 + tps) : ntiles_all;      // this block's tiles: [tl0, ntiles)
+    const TileRange mine_t = SLICED ? slice_tiles(ntiles_all, n_slices, slice) : TileRange{0, ntiles_all};     // (the host's rule too: no slice is empty)
+    const int tl0 = mine_t.lo, ntiles = mine_t.hi;                // this block's tiles: [tl0, ntiles)
     fetch_rows(tl0 * DZI_TS);
     issue();
     fetch_rows((tl0 + 1) * DZI_TS);
@@ -1588,36 +1565,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         for (int e = tid; e < CH_F4; e += 256) finish(e, *reinterpret_cast<const float4*>(s_dv + 4 * e));
         return;
     }
-    // ---- S > 1: park the partial, be counted, the last one adds them up (pass 2's hand-off: write-through stores, vmcnt(0), a device-scope
-    // counter, device-scope loads)
+    // ---- S > 1: park the partial, be counted, the last one adds them up (pass 2's hand-off)
     constexpr int SLAB_F = p3_slab_floats(CP);
     float* const mine = slab + ((int64_t)slice * nchunks + chunk) * SLAB_F;
-    for (int e = tid; e < CH_F4; e += 256) {
-        const float4 g4 = *reinterpret_cast<const float4*>(s_dv + 4 * e);
-        __hip_atomic_store(mine + 4 * e + 0, g4.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 4 * e + 1, g4.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 4 * e + 2, g4.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 4 * e + 3, g4.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __shared__ int s_last;
-    __builtin_amdgcn_s_waitcnt(0x0F70);                               // vmcnt(0): this wave's stores have been acknowledged ...
-    __syncthreads();
-    if (tid == 0) {
-        const int old = __hip_atomic_fetch_add(&slice_cnt[chunk], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... before the block is counted
-        s_last = old == n_slices - 1;
-        if (s_last) __hip_atomic_store(&slice_cnt[chunk], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // ready for the next launch
-    }
-    __syncthreads();
-    if (!s_last) return;                                              // block-uniform
+    for (int e = tid; e < CH_F4; e += 256) handoff_put4(mine + 4 * e, *reinterpret_cast<const float4*>(s_dv + 4 * e));
+    if (!handoff_count_last(&slice_cnt[chunk], n_slices)) return;     // block-uniform
     for (int e = tid; e < CH_F4; e += 256) {
         float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int sl = 0; sl < n_slices; ++sl) {                       // slice order, whoever is last
-            const float* part = slab + ((int64_t)sl * nchunks + chunk) * SLAB_F + 4 * e;
-            g4.x += __hip_atomic_load(part + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g4.y += __hip_atomic_load(part + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g4.z += __hip_atomic_load(part + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g4.w += __hip_atomic_load(part + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        for (int sl = 0; sl < n_slices; ++sl) handoff_add4(g4, slab + ((int64_t)sl * nchunks + chunk) * SLAB_F + 4 * e);         // slice order, whoever is last
         finish(e, g4);
     }
 }
@@ -1900,6 +1855,23 @@ extern "C" int nadm_pca_project(const uint8_t* xp, int64_t ld, const int32_t* id
     return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0x3FC0u);
 }
 
+// ---- sample slices, the host's side of slice_tiles (nadm_common.h), shared by passes 2 and 3: the n_slices argument of a pass, refused
+// in the entry point's own words (`no_kernel`: why this shape has no sliced kernel, or NULL)
+static int slice_args(int32_t n_slices, int tiles, const float* slab, const int32_t* counters, const char* out_of_range, const char* no_kernel,
+                      const char* no_slab, const char* empty_slice) {
+    if (n_slices < 1 || n_slices > NADM_MAX_P2_SLICES) return fail(out_of_range);
+    if (n_slices == 1) return 0;
+    if (no_kernel) return fail(no_kernel);
+    if (!slab || !counters || ((uintptr_t)slab & 15)) return fail(no_slab);
+    return slices_leave_one_empty(tiles, n_slices) ? fail(empty_slice) : 0;
+}
+// the most slices any batch of up to bmax rows is cut into: the rule of the pass at every tile count
+static int32_t slices_max(int32_t (*rule)(int32_t, int64_t, int32_t), int32_t bmax, int64_t M, int32_t width, int tile_rows) {
+    int32_t mx = 1;
+    for (int32_t b = bmax; b > 0; b -= tile_rows) { const int32_t s = rule(b, M, width); if (s > mx) mx = s; }
+    return mx;
+}
+
 static int decode_bce_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                            float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
                            float* losspart, int32_t with_loss, void* stream, uint8_t* xg, AdamFused ad, const uint4* qimg = nullptr,
@@ -1908,14 +1880,11 @@ static int decode_bce_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, in
     if (medium && kp <= 16 && (!qimg || NADM_BF_TS != nadm::QI_TS))        // (kp > 16: the VALU kernel, the same under either precision)
         return fail("nadm_step: precision \"medium\" runs pass 2 from the Q images (nadm_plan_desc_t.qimg) at padded K <= 16");
     if (ld >> 32) return fail("nadm_decode_bce: rows of 4 GiB and more (ld >= 2^32) are not supported");      // the matrix pass forms row addresses from 32-bit factors
-    if (n_slices < 1 || n_slices > NADM_MAX_P2_SLICES) return fail("nadm_decode_bce_sliced: n_slices must be in 1..8");
-    if (n_slices > 1) {
-        if (kp > 16) return fail("nadm_decode_bce_sliced: sample slices exist for padded K <= 16 only");
-        if (!slab || !slice_cnt || ((uintptr_t)slab & 15)) return fail("nadm_decode_bce_sliced: n_slices > 1 needs the slab (16-byte aligned) and the counters");
-        const int tiles = (b + NADM_BF_TS - 1) / NADM_BF_TS, tps = (tiles + n_slices - 1) / n_slices;
-        if ((int64_t)(n_slices - 1) * tps >= tiles) return fail("nadm_decode_bce_sliced: a slice would be empty (take n_slices from nadm_decode_slices)");
-    }
-    if (qimg && (kp > 16 || NADM_BF_TS != nadm::QI_TS)) return fail("nadm_decode_bce_images: Q images exist for padded K <= 16 only");
+    if (slice_args(n_slices, (b + NADM_BF_TS - 1) / NADM_BF_TS, slab, slice_cnt, "nadm_decode_bce_sliced: n_slices must be in 1..8",
+                   kp > 16 ? "nadm_decode_bce_sliced: sample slices exist for padded K <= 16 only" : nullptr,
+                   "nadm_decode_bce_sliced: n_slices > 1 needs the slab (16-byte aligned) and the counters",
+                   "nadm_decode_bce_sliced: a slice would be empty (take n_slices from nadm_decode_slices)")) return 1;
+    if (qimg &&(kp > 16 || NADM_BF_TS != nadm::QI_TS)) return fail("nadm_decode_bce_images: Q images exist for padded K <= 16 only");
     if ((uintptr_t)qimg & 15) return fail("nadm_decode_bce_images: qimg must be 16-byte aligned");
     if (with_loss < 0 || with_loss > 3) return fail("nadm_decode_bce: with_loss is a bit set (1: loss value, 2: P may lie outside [0,1])");
     if (!(with_loss & 1)) with_loss = 0;
@@ -1995,17 +1964,10 @@ extern "C" int32_t nadm_decode_slices(int32_t b, int64_t M, int32_t kp) {
         if (s > lim) s = (int)lim;
         if (s > NADM_MAX_P2_SLICES) s = NADM_MAX_P2_SLICES;
     }
-    if (s > tiles) s = tiles;
-    if (s < 2) return 1;
-    const int tps = (tiles + s - 1) / s;
-    return (tiles + tps - 1) / tps;                                   // no empty slice
+    return slices_without_empty(tiles, s);
 }
 
-extern "C" int32_t nadm_decode_slices_max(int32_t bmax, int64_t M, int32_t kp) {       // the most slices any batch of up to bmax rows is cut into
-    int32_t mx = 1;
-    for (int32_t b = bmax; b > 0; b -= NADM_BF_TS) { const int32_t s = nadm_decode_slices(b, M, kp); if (s > mx) mx = s; }
-    return mx;
-}
+extern "C" int32_t nadm_decode_slices_max(int32_t bmax, int64_t M, int32_t kp) { return slices_max(nadm_decode_slices, bmax, M, kp, NADM_BF_TS); }
 
 extern "C" int64_t nadm_decode_slab_floats(int64_t M, int32_t kp, int32_t n_slices) {
     if (kp > 16 || n_slices < 2 || M <= 0) return 0;
@@ -2086,10 +2048,9 @@ static int encode_bwd_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, in
             side.Zn = mw->Zn; side.H = mw->H; side.dL = mw->dL; side.dHpre = mw->dHpre; side.dgp = mw->dgp; side.small_part = mw->small_part;
             extra = (int64_t)side.gx * nadm_sample_splits(b);
         }
-        if (n_slices < 1 || n_slices > NADM_MAX_P2_SLICES) return fail("nadm_encode_bwd_sliced: n_slices must be in 1..8");
-        const int ntiles = (b + DZI_TS - 1) / DZI_TS;
-        if (n_slices > 1 && ((n_slices - 1) * ((ntiles + n_slices - 1) / n_slices) >= ntiles)) return fail("nadm_encode_bwd_sliced: an empty sample slice");
-        if (n_slices > 1 && (!slab || !counters || ((uintptr_t)slab & 15))) return fail("nadm_encode_bwd_sliced: the slab (16-byte aligned) and the counters are NULL");
+        if (slice_args(n_slices, (b + DZI_TS - 1) / DZI_TS, slab, counters, "nadm_encode_bwd_sliced: n_slices must be in 1..8", nullptr,
+                       "nadm_encode_bwd_sliced: the slab (16-byte aligned) and the counters are NULL",
+                       "nadm_encode_bwd_sliced: an empty sample slice")) return 1;
         dim3 g2((unsigned)(((M + EB_CHUNK_SNPS - 1) / EB_CHUNK_SNPS) * n_slices + extra));
 #define NADM_P3_LAUNCH(CPV, CL, SL) hipLaunchKernelGGL((encode_bwd_fp4_kernel<CPV, CL, SL>), g2, block, 0, st, xp, ld, idx, b, M, (const uint4*)dzimg, dV, missing_bf16, Vrw, ad, side, slab, counters, (int)n_slices)
         const bool clean = (flags & NADM_X_CLEAN) != 0 && missing_bf16 == 0u;
@@ -2139,17 +2100,10 @@ extern "C" int32_t nadm_encode_slices(int32_t b, int64_t M, int32_t cp) {
         if (chunks >= 192 || tiles < 32) return 1;
         s = 2;
     }
-    if (s > tiles) s = tiles;
-    if (s < 2) return 1;
-    const int tps = (tiles + s - 1) / s;
-    return (tiles + tps - 1) / tps;                                   // no empty slice
+    return slices_without_empty(tiles, s);
 }
 
-extern "C" int32_t nadm_encode_slices_max(int32_t bmax, int64_t M, int32_t cp) {
-    int32_t mx = 1;
-    for (int32_t b = bmax; b > 0; b -= DZI_TS) { const int32_t s = nadm_encode_slices(b, M, cp); if (s > mx) mx = s; }
-    return mx;
-}
+extern "C" int32_t nadm_encode_slices_max(int32_t bmax, int64_t M, int32_t cp) { return slices_max(nadm_encode_slices, bmax, M, cp, DZI_TS); }
 
 extern "C" int64_t nadm_encode_slab_floats(int64_t M, int32_t cp, int32_t n_slices) {
     if (cp > 8 || n_slices < 2 || M <= 0) return 0;

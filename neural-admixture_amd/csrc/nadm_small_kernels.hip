@@ -763,7 +763,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_a_fast_kernel(nadm_heads_t hd, co
                 dgv = dzn[c] * z * ri;
             }
             // (image path: written THROUGH to memory -- the group's last block, possibly on another XCD with its own L2, reads it back)
-            if (dzimg != nullptr) __hip_atomic_store(dZ + i * CP + c, dz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (dzimg != nullptr) handoff_put(dZ + i * CP + c, dz);
             else dZ[i * CP + c] = dz;
             dgp[i * CP + c] = dgv;
         }
@@ -772,27 +772,16 @@ __global__ __launch_bounds__(256) void mlp_bwd_a_fast_kernel(nadm_heads_t hd, co
     // samples of one column = the rows of 32 / SB blocks of this launch.  The block that finishes a group of 32 samples LAST builds
     // the group's image (one wave: 8 columns x 8 pieces); the counters return to zero for the next launch.  (As a launch of its own
     // the image cost 5 us + a launch gap per step, more than the matrix instruction saved in pass 3.)
-    // Ordering without a fence: the dZ stores above go through to memory (a __threadfence here is a write-back of the XCD's whole L2,
-    // which this kernel has just filled with dHpre: 200 of them took the kernel from 17 to 36-42 us), the wave waits for their
-    // acknowledgement, then the block is counted with a device-scope atomic; the last block reads with device-scope loads.
+    // Ordering without a fence (the park-and-count hand-off of nadm_common.h): a __threadfence here is a write-back of the XCD's whole L2,
+    // which this kernel has just filled with dHpre: 200 of them took the kernel from 17 to 36-42 us.
     if (dzimg != nullptr) {
-        __shared__ int s_last;
-        __builtin_amdgcn_s_waitcnt(0x0F70);                           // vmcnt(0): this wave's dZ stores have been acknowledged ...
-        __syncthreads();
         const int grp = i0 / 32;
-        if (tid == 0) {
-            const int in_group = (min(b, 32 * grp + 32) - 32 * grp + SB - 1) / SB;
-            const int old = __hip_atomic_fetch_add(&dzcnt[grp], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ... before the block is counted
-            s_last = old == in_group - 1;
-            if (s_last) __hip_atomic_store(&dzcnt[grp], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (s_last) {                                                 // block-uniform
+        if (handoff_count_last(&dzcnt[grp], [&] { return (min(b, 32 * grp + 32) - 32 * grp + SB - 1) / SB; })) {      // the group's blocks; block-uniform
             // the group's 32 x 8 values: ONE load per thread, parked in LDS; 64 threads then cut a column's 32 values into a piece each
             float* const s_grpz = s_part;                             // (free since the block reduction)
             const int smp = 32 * grp + (tid >> 3), cc = tid & 7;
             float x = 0.f;
-            if (smp < b && cc < CP) x = __hip_atomic_load(dZ + (int64_t)smp * CP + cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (smp < b && cc < CP) x = handoff_get(dZ + (int64_t)smp * CP + cc);
             s_grpz[tid] = x;
             __syncthreads();
             if (tid < 64) dzi_build_piece<true>(s_grpz, b, CP, dzimg, grp >> 2, grp & 3, tid >> 3, tid & 7);

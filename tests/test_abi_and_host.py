@@ -58,6 +58,35 @@ def test_argument_validation_without_gpu():
         check(lib.nadm_heads_init(C.byref(h), 8, 64, ks, 1), "heads_init")
 
 
+def test_sliced_passes_refuse_their_slice_arguments_without_gpu():
+    """nadm_decode_bce_sliced / nadm_encode_bwd_sliced: n_slices outside 1..8, a missing or misaligned slab, missing counters, a shape
+    without a sliced kernel and a count that leaves a slice empty (5 tiles in 4 slices: 2 tiles each, the fourth has none) are refused,
+    each pass in its own words, before anything is launched -- the pointers are never dereferenced."""
+    from neural_admixture_amd._lib import lib, check
+    fake, odd = C.c_void_p(0x1000), C.c_void_p(0x1008)
+
+    def pass2(n_slices, slab=fake, counters=fake, kp=8, b=320):          # (M = 0: whatever the slice checks let through is refused after them)
+        return lib.nadm_decode_bce_sliced(fake, 16, fake, b, 0, fake, kp, fake, 8, fake, fake, None, 0, None, None, None, n_slices, slab, counters, None)
+
+    def pass3(n_slices, slab=fake, counters=fake, cp=8, b=640):
+        return lib.nadm_encode_bwd_sliced(fake, 16, fake, b, 64, fake, fake, cp, None, fake, None, None, 0, n_slices, slab, counters, None)
+
+    for call, who, no_slab, empty in (
+            (pass2, "nadm_decode_bce_sliced", "nadm_decode_bce_sliced: n_slices > 1 needs the slab (16-byte aligned) and the counters",
+             "nadm_decode_bce_sliced: a slice would be empty (take n_slices from nadm_decode_slices)"),
+            (pass3, "nadm_encode_bwd_sliced", "nadm_encode_bwd_sliced: the slab (16-byte aligned) and the counters are NULL",
+             "nadm_encode_bwd_sliced: an empty sample slice")):
+        for rc, msg in ((lambda: call(0), who + ": n_slices must be in 1..8"), (lambda: call(9), who + ": n_slices must be in 1..8"),
+                        (lambda: call(2, slab=None), no_slab), (lambda: call(2, counters=None), no_slab), (lambda: call(2, slab=odd), no_slab),
+                        (lambda: call(4), empty)):
+            with pytest.raises(RuntimeError, match=re.escape(msg)):
+                check(rc(), who)
+    with pytest.raises(RuntimeError, match=re.escape("nadm_decode_bce_sliced: sample slices exist for padded K <= 16 only")):
+        check(pass2(2, kp=24), "decode_bce_sliced")
+    with pytest.raises(RuntimeError, match=re.escape("nadm_encode_bwd_sliced: the matrix-core pass only (C <= 8)")):
+        check(pass3(2, cp=12), "encode_bwd_sliced")
+
+
 def test_argument_validation_of_the_round1_additions(tmp_path):
     """Error paths of the entry points added after the core path: every one fails with a message before any launch."""
     from neural_admixture_amd._lib import lib, check
@@ -863,19 +892,13 @@ def test_pack2bit_module_has_the_reference_names_and_refuses_misplaced_tensors()
         pack2bit.unpack2bit_gpu_to_gpu(torch.zeros((3, 3), dtype=torch.uint8), g)
 
 
-def test_dz_image_hand_off_compiles_to_the_instructions_its_contract_names(tmp_path):
-    """the cross-block hand-off of the dZ image (mlp_bwd_a kernels) is ordered without a fence.  What it relies on is
-    which INSTRUCTIONS the compiler emits: write-through payload stores (`global_store_dword ... sc1`), `s_waitcnt vmcnt(0)` before the
-    block is counted, a returning device-scope counter update (`global_atomic_add ... sc0`), and `sc1` loads by the block that arrives
-    last.  A toolchain upgrade that changes any of them shows up here, not as a one-in-a-million wrong gradient."""
-    import shutil
+def _kernels_that_count_blocks(unit, tmp_path):
+    """{mangled kernel name: its instruction lines} of the kernels of csrc/<unit>.hip that hold a `global_atomic_add`, from `hipcc -S` of
+    the device side alone."""
     import subprocess
-    if shutil.which("hipcc") is None:
-        pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "neural-admixture_amd", "csrc", "nadm_small_kernels.hip")
-    out = tmp_path / "small.s"
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", str(out), src],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    out = tmp_path / (unit + ".s")
+    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", str(out),
+                    os.path.join(ROOT, "neural-admixture_amd", "csrc", unit + ".hip")], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     funcs, cur = {}, None
     for line in open(out):
         if line.startswith("_Z") and ":" in line:              # "<mangled name>:   ; @<mangled name>"
@@ -883,14 +906,32 @@ def test_dz_image_hand_off_compiles_to_the_instructions_its_contract_names(tmp_p
             funcs[cur] = []
         elif cur is not None and line.startswith("\t") and not line.startswith("\t."):
             funcs[cur].append(line.strip())
-    kernels = {k: v for k, v in funcs.items() if "mlp_bwd_a" in k and any(i.startswith("global_atomic_add ") for i in v)}
+    return {k: v for k, v in funcs.items() if any(i.startswith("global_atomic_add ") for i in v)}
+
+
+def test_dz_image_hand_off_compiles_to_the_instructions_its_contract_names(tmp_path):
+    """csrc/nadm_common.h, the park-and-count hand-off: the dZ image (mlp_bwd_a kernels) and the partial sums of
+    the sliced passes 2 and 3 go from block to block without a fence.  What that relies on is
+    which INSTRUCTIONS the compiler emits: write-through payload stores (`global_store_dword ... sc1`), `s_waitcnt vmcnt(0)` before the
+    block is counted, a returning device-scope counter update (`global_atomic_add ... sc0`), and `sc1` loads by the block that arrives
+    last.  A toolchain upgrade that changes any of them shows up here, not as a one-in-a-million wrong gradient.  Held to it: the
+    image-building instantiations of the MLP backward and EVERY kernel of the passes' unit that counts blocks -- the 36 sliced
+    instantiations of pass 2 and the 4 of pass 3 (each unit is compiled once, here)."""
+    import shutil
+    if shutil.which("hipcc") is None:
+        pytest.skip("no hipcc")
+    small = _kernels_that_count_blocks("nadm_small_kernels", tmp_path)
+    kernels = {k: v for k, v in small.items() if "mlp_bwd_a" in k}
     assert len(kernels) >= 2                                   # the instantiations of the MLP backward that build the image
+    passes = _kernels_that_count_blocks("nadm_genotype_passes", tmp_path)
+    assert sum("decode_bce_bf16" in k for k in passes) >= 36 and sum("encode_bwd_fp4" in k for k in passes) >= 4      # (a filter that matches nothing cannot pass)
+    kernels.update(passes)
     for name, ins in kernels.items():
         at = [i for i, s_ in enumerate(ins) if s_.startswith("global_atomic_add ")]
         assert len(at) == 1 and ins[at[0]].endswith("sc0"), (name, [ins[i] for i in at])       # ONE counter update, returning the old value
         before, after = ins[: at[0]], ins[at[0] + 1:]
         st = [i for i, s_ in enumerate(before) if s_.startswith("global_store_dword ") and s_.endswith(" sc1")]
-        assert st, name                                        # the dZ payload goes through to memory
+        assert st, name                                        # the payload goes through to memory
         waits = [i for i, s_ in enumerate(before) if s_.startswith("s_waitcnt") and "vmcnt(0)" in s_ and i > st[-1]]
         assert waits, name                                     # ... and is acknowledged before the block is counted
         assert any(s_.startswith("s_barrier") for s_ in before[waits[-1]:]), name      # every wave of the block has waited
