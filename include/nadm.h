@@ -865,6 +865,44 @@ int nadm_resid_cor(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t b
                    const float* B, const float* C, float eps, double* S, double* Ta, double* Tb, int32_t* nobs,
                    float* scratch, void* stream);
 
+/* ---- the observed-calls pair products: what a centred, scaled, missing-aware PCA of the packed matrix is made of ----------------
+ * nadm_pca_project* restate the reference's initialisation (raw codes, missing = 3, no centring); a PCA anyone would plot
+ * (smartpca, plink --pca, FastPCA) standardises each SNP and leaves a missing call at the mean.  That product cannot be had from
+ * them by algebra: it needs the product with the observation indicator as well.  One call = the rows idx[0..b) (idx == NULL: rows
+ * 0..b; any order, a duplicate counts as often as it occurs).  Codes g in {0, 1, 2} are observed, 3 is missing; o_sj = 1 where the
+ * call is observed and j < M, else 0:
+ *     nadm_obs_project     Y[s, c]  = sum_j (g o)_sj W1[j, c] + o_sj W2[j, c]                      Y  float [b, CP]
+ *     nadm_obs_project_t   O1[j, c] = sum_s (g o)_sj Yin[s, c]      O2[j, c] = sum_s o_sj Yin[s, c]        O1, O2 float [M, CP]
+ * W1, W2 float [M, CP], Yin float [b, CP] (row s belongs to idx[s]).  C in 1..CP columns are in use, CP in {16, 32} is the column
+ * stride; pad columns are zero on input and are written as zero.  The centring and scaling are the caller's: W1 = s o W and
+ * W2 = -c o s o W give sum_j o (g - c_j) s_j W_j, and s_j (O1_j - c_j O2_j) is the transposed product (neural_admixture_amd/pca.py).
+ * b in 1..NADM_OBS_MAX_ROWS.  scratch: nadm_obs_project_scratch_floats(b, M, CP) / nadm_obs_project_t_scratch_floats(b, M, CP)
+ * floats (both grow with b and M).  xp, W1, W2, Yin, Y, O1, O2, scratch 16-byte, idx 4-byte aligned; ld >= ceil(M/4), ld % 16 == 0,
+ * ld < 2^32; the address of row r is r * ld in 64 bits.
+ * Arithmetic: g o in {0, 1, 2} and o in {0, 1} are exact in one bf16 piece; an fp32 operand value is cut into three
+ * round-to-nearest bf16 pieces (exact: 3 x 8 significand bits) and multiplied on the matrix pipe (v_mfma_f32_16x16x32_bf16), lo, mid,
+ * hi piece in that order, every product exact, the sums fp32.  Forward: the 256-SNP chunks are cut into nadm_obs_project_ranges(b, M)
+ * contiguous ranges of nadm_obs_project_chunks(b, M) chunks (more than one range while the 256-sample tiles of the block alone do
+ * not fill the chip); both terms of a SNP go into ONE fp32 accumulator, which never covers more than 2^18 SNPs.  Transposed: the
+ * batch's 64-sample tiles are cut into nadm_obs_project_t_slices(b, M) slices of whole tiles -- the rule of nadm_snp_hwe_slices:
+ * never more than 4096 samples in one fp32 accumulator.  The ranges' / slices' partials are added in float64 in range / slice
+ * order and rounded to fp32 once.  The order depends on (b, M, CP) alone and there are no floating-point atomics: the same inputs
+ * give the same bits.
+ * A missing call, a SNP >= M, a row past the list, the pad bits of a row's last byte and the bytes behind it enter every sum as
+ * exactly +0.0f: an all-missing row gives a Y row of +0.0, and rows >= M of W1 / W2 are never read.  (Where a call is missing the
+ * operand value is still multiplied by that 0: operands must be finite.)
+ * Every refusal -- a null pointer, an empty block, ld, C / CP, alignment, b -- is reported before anything is launched. */
+#define NADM_OBS_MAX_ROWS (1 << 24)
+int32_t nadm_obs_project_chunks(int32_t b, int64_t M);
+int32_t nadm_obs_project_ranges(int32_t b, int64_t M);
+int64_t nadm_obs_project_scratch_floats(int32_t b, int64_t M, int32_t CP);
+int nadm_obs_project(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* W1, const float* W2,
+                     int32_t C, int32_t CP, float* Y, float* scratch, void* stream);
+int32_t nadm_obs_project_t_slices(int32_t b, int64_t M);
+int64_t nadm_obs_project_t_scratch_floats(int32_t b, int64_t M, int32_t CP);
+int nadm_obs_project_t(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* Yin, int32_t C,
+                       int32_t CP, float* O1, float* O2, float* scratch, void* stream);
+
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,
  * random_state=seed).fit(X).means_): the EM iterations of that call in float64 on the host (csrc/nadm_gmm.cpp restates the

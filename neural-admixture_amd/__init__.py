@@ -18,9 +18,11 @@ from .cv import cv_error, mask_fold, heldout_deviance    # noqa: F401  (cross-va
 from .bootstrap import bootstrap_q, block_weights    # noqa: F401  (bootstrap standard errors of Q: SNPs resampled, weighted refits)
 from .pse import p_se, p_info, se_from_info    # noqa: F401  (standard errors of P: per-SNP Fisher information given Q, inverted)
 from .fitcheck import resid_cor, em_sums, fit_check, group_means, sample_means    # noqa: F401  (model-fit check: correlation of leave-one-out residuals)
+from . import pca                 # noqa: F401  (principal components of the standardised genotypes: pca.pca; the module, whose name its function shares)
+from .pca import obs_project, obs_project_t    # noqa: F401  (its two products: the observed-calls pair products)
 from . import pack2bit            # noqa: F401  (the reference's native module by its own names: pack2bit.cu:144-147)
 
 __all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish", "kinship", "kinship_pairs",
            "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep", "cv_error", "mask_fold", "heldout_deviance",
            "bootstrap_q", "block_weights", "p_se", "p_info", "se_from_info", "resid_cor", "em_sums", "fit_check", "group_means",
-           "sample_means"]
+           "sample_means", "pca", "obs_project", "obs_project_t"]

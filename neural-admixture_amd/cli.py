@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv|bootstrap|pse|fit ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv|bootstrap|pse|fit|pca ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -160,6 +160,21 @@ def parse_prune_args(argv):
     _add_run_args(p, multi_k=None, out=None)
     p.add_argument("--window", type=int, default=50, help="a SNP is compared with its next window - 1 neighbours on its chromosome (default 50)")
     p.add_argument("--r2", type=float, default=0.1, help="of a pair with an r^2 above this the SNP with the smaller minor-allele frequency goes (default 0.1)")
+    return p.parse_args(argv)
+
+
+def parse_pca_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture pca",
+                                description="Principal components of the standardised genotypes (the GRM of smartpca / plink --pca), "
+                                            "from the genotype file alone")
+    _add_run_args(p, multi_k=None, out="eigenvalues and eigenvectors")
+    p.add_argument("--pcs", type=int, default=10, help="principal components to report (default 10)")
+    p.add_argument("--oversample", type=int, default=10,
+                   help="extra columns the subspace iteration carries (default 10); --pcs + --oversample is at most 32")
+    p.add_argument("--iters", type=int, default=10, help="rounds of subspace iteration (default 10, FastPCA's)")
+    p.add_argument("--maf", type=float, default=0.0,
+                   help="leave out the SNPs whose minor-allele frequency is below this (default 0: only unobserved and monomorphic SNPs go)")
+    p.add_argument("--seed", type=int, default=42)
     return p.parse_args(argv)
 
 
@@ -394,6 +409,31 @@ def _prune_main(argv):
     log.info(f"    LD pruning (window {args.window}, r2 {args.r2:g}): {stats['kept']} SNPs kept, {stats['removed']} removed "
              f"({stats['seconds']:.2f} seconds; {stats['ranges']} ranges).")
     log.info("    SNP lists saved.")
+
+
+def _pca_main(argv):
+    """``pca`` mode: the genotypes alone -> {out_name}.eigenval (one eigenvalue per line) and {out_name}.eigenvec (plink's layout: two
+    identifier columns, here the 0-based sample index as the ``kinship`` mode names samples, then PC1 ..)."""
+    from . import pca
+    args = parse_pca_args(argv)
+    try:
+        pca.check_args(args.pcs, args.oversample, args.iters, args.maf)
+    except RuntimeError as e:
+        raise SystemExit(f"    {e}") from None
+    keep = _extract_keep(args.data_path, args.extract)     # before the GPU check and before any genotype is read
+    name = os.path.basename(args.data_path)
+    if ".vcf" in name:
+        if not os.path.isfile(args.data_path):
+            raise SystemExit(f"    {args.data_path} not found.")
+    elif ".bed" in name:
+        _bed_shape(args.data_path, need_bim=False)
+    else:
+        raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
+    data = _read_on_gpu(args, keep)
+    res = pca.pca(data.packed, data.M, pcs=args.pcs, oversample=args.oversample, iters=args.iters, maf=args.maf, seed=args.seed)
+    pca.log_result(res, log)
+    pca.write_result(_out_stem(args), res)
+    log.info("    Eigenvalues and eigenvectors saved.")
 
 
 def _hwe_main(argv):
@@ -660,14 +700,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 
 _ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
-                   "pse": _pse_main, "fit": _fit_main}
+                   "pse": _pse_main, "fit": _fit_main, "pca": _pca_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "fit"), \
+    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "fit", "pca"), \
         ('Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions, '
-         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "fit" checks the fit sample by sample).')
+         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         _ANALYSIS_MODES[mode](argv[1:])

@@ -664,6 +664,15 @@ class Engine:
                        max_k=(fitcheck.MAX_K, fitcheck.TOO_WIDE))
         return fitcheck.resid_cor(self.xp, self.M, *self._fitted(head), pairs_idx=pairs_idx, rows=rows)
 
+    def pca(self, pcs: int = 10, oversample: int = 10, iters: int = 10, maf: float = 0.0, seed: int = 42):
+        """Principal components of the resident matrix's standardised genotypes (pca.pca; include/nadm.h, nadm_obs_project /
+        nadm_obs_project_t): a ``PcaResult`` with ``eigenvalues`` ``[pcs]``, ``eigenvectors`` ``[N, pcs]``, ``M_eff`` and
+        ``explained``.  It reads the genotypes alone, not the model; the engine's parameters and optimiser state are left as they
+        are."""
+        from . import pca
+        self._analysis("pca", "use pca.pca on one GPU from the genotype file")
+        return pca.pca(self.xp, self.M, pcs=pcs, oversample=oversample, iters=iters, maf=maf, seed=seed)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()
