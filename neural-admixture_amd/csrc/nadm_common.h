@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/nadm.h"
+#include "nadm_pass_args.h"     // the shape constants the host rules share, the sample-slice rule, AdamFused
 
 namespace nadm {
 
@@ -44,19 +45,6 @@ __device__ __forceinline__ uint32_t obs_mask(uint32_t code) {
     asm("" : "+v"(m));
     return m;
 }
-
-// ---- sample slices of the sliced passes 2 and 3: ONE rule for the kernels and for the host code that chooses and checks n_slices ----------
-// Slice s walks tiles [s tps, min(tiles, s tps + tps)), tps = ceil(tiles / n_slices).  The host refuses a count that leaves the last slice
-// empty: it would never be counted and the hand-off below would never complete.
-struct TileRange { int lo, hi; };
-__host__ __device__ constexpr int slice_tps(int tiles, int n_slices) { return (tiles + n_slices - 1) / n_slices; }
-__host__ __device__ constexpr TileRange slice_tiles(int tiles, int n_slices, int slice) {
-    const int tps = slice_tps(tiles, n_slices), lo = slice * tps;
-    return TileRange{lo, tiles < lo + tps ? tiles : lo + tps};
-}
-__host__ __device__ constexpr bool slices_leave_one_empty(int tiles, int n_slices) { return slice_tiles(tiles, n_slices, n_slices - 1).lo >= tiles; }
-// the largest count <= min(s, tiles) that leaves no slice empty; 1 = unsliced
-__host__ __device__ constexpr int slices_without_empty(int tiles, int s) { return s < 2 || tiles < 2 ? 1 : slice_tps(tiles, slice_tps(tiles, s < tiles ? s : tiles)); }
 
 // ---- the park-and-count hand-off between blocks of one launch ---------------------------------------------------------------------------
 // Users: the sliced pass 2 (decode_bce_bf16_kernel: a chunk's dP and loss partials), the sliced pass 3 (encode_bwd_fp4_kernel: the dV
@@ -150,14 +138,10 @@ __device__ __forceinline__ double wave_sum_all_f64(double v) {
 }
 
 // ---- Adam element (torch.optim.Adam closed form, betas .9/.95, eps 1e-8; neural_admixture.py:187-204) + restrict_P ----
-// inv_bc2 = 1 / sqrt(1 - 0.95^t), step_size = lr / (1 - 0.9^t): nadm_host.h adam_scalars
+// inv_bc2 = 1 / sqrt(1 - 0.95^t), step_size = lr / (1 - 0.9^t): nadm_host_rules.h adam_scalars
 // One definition for the stand-alone kernel and for the epilogues of passes 2 and 3 that apply the update to the rows whose
 // gradient they have just completed: the same operations in the same order, hence the same bits.
-struct AdamFused {            // m == nullptr: no fused update
-    float* m;
-    float* v;
-    float step_size, inv_bc2, grad_scale;
-};
+// (AdamFused, the arguments of a fused update: nadm_pass_args.h)
 __device__ __forceinline__ float adam_element(float p, float g, float& m, float& v, float step_size, float inv_bc2,
                                               float grad_scale, bool clamp01) {
     const float b2 = 0.95f, eps = 1e-8f;
@@ -211,8 +195,7 @@ __device__ __forceinline__ void split3(float v, uint32_t& h, uint32_t& m, uint32
 // > the block's largest magnitude, n = |v| / 2^(E0 - 28) < 2^32, piece p = hexadecimal digit p of n with the sign of v.  Digit h is the
 // FP6 (E2M3) number h / 8 exactly, so piece p enters with the scale 2^(E0 - 4p + 3).  An element within 2^-8 of the block maximum is
 // carried exactly, a smaller one to an absolute error < 2^-31 of that maximum.
-constexpr int DZI_TS = 128;
-constexpr int DZI_TILE_U4 = 7 * 64;
+// (DZI_TS = 128 samples per tile, DZI_TILE_U4 = 7 * 64: nadm_pass_args.h)
 // sample (within its tile) of element e = 0..31 of K-block q: the order pass 3's bit transposition produces (see there)
 __host__ __device__ constexpr int dzi_sample(int q, int e) { return 32 * q + 8 * (e >> 3) + 4 * (e & 1) + ((e & 7) >> 1); }
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
@@ -285,8 +268,7 @@ __device__ __forceinline__ void dzi_build_piece(const float* dZ, int b, int CP, 
 //   [512, 512 + 128 W2) dP operands   [sample pair 0..1][operand 0 .. W2-1][lane]          W2 = 1 for K <= 8, 2 for K 9..16
 // with the slot assignment of decode_bce_bf16_kernel (see there).  Slots that hold no piece are zero and are never written:
 // the buffer must be zero-filled once.  Rows b .. 64*ceil(b/64)-1 of the last tile are written as zeros by the producer.
-constexpr int QI_TS = 64;                                  // samples per tile (= NADM_BF_TS of the pass-2 build)
-constexpr int QI_TILE_U4 = 768;                            // uint4 per tile image in global memory (K <= 8 uses the first 640)
+// (QI_TS = 64 samples per tile, QI_TILE_U4 = 768 uint4 per tile image in global memory: nadm_pass_args.h)
 __device__ __host__ constexpr int qi_tile_u4(int kp) { return kp > 8 ? 768 : 640; }
 // element (sample qr of the tile, column qk of the head) with value v -> its pieces in the tile image `img` (uint16 view)
 __device__ __forceinline__ void q_image_put(uint16_t* __restrict__ img, const int kp, const int qr, const int qk, const float v) {

@@ -1,5 +1,5 @@
 // The per-thread error message behind nadm_last_error(): plain C++, no HIP header, so that the host-only units
-// (nadm_host_io.cpp, nadm_layout.cpp, nadm_gmm.cpp) build with any C++ compiler.
+// (nadm_host_io.cpp, nadm_layout.cpp, nadm_gmm.cpp, nadm_passes_host.cpp) build with any C++ compiler.
 #pragma once
 #include <stdio.h>
 #include <string.h>

@@ -9,6 +9,9 @@
 // in registers, never materialised (the reference unpacks to uint8 [b,M] and then to fp32 [b,M]
 // every step: pack2bit.cu:38-62, neural_admixture.py:404-406,169-170).
 //
+// This unit holds the kernels and, at its end, one launcher per launch struct (nadm_pass_args.h).  The C entry points, the argument
+// checks and the rules that choose the form, the slices and the grid split are host code of their own: nadm_passes_host.cpp.
+//
 // All three kernels stream X tiles HBM -> LDS with 16-byte-per-lane coalesced loads of whole row
 // segments (>= 128 B contiguous per gathered row), software-prefetched one tile ahead.
 #include "nadm_common.h"
@@ -130,10 +133,7 @@ __global__ void encode_fwd_kernel(const uint8_t* __restrict__ xp, int64_t ld, co
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-constexpr int EM_WAVES = 8;
-constexpr int EM_SLICE = 256;                         // SNPs per wave
-constexpr int EM_CHUNK_SNPS = EM_WAVES * EM_SLICE;    // 2048
-constexpr int EM_TILES_PER_BLOCK = 52;                // upper bound of 16-sample tiles per block (grid.y splits the batch)
+// (EM_WAVES = 8 waves x EM_SLICE = 256 SNPs = EM_CHUNK_SNPS, EM_TILES_PER_BLOCK: nadm_pass_args.h)
 #ifndef NADM_EM_D
 #define NADM_EM_D 4
 #endif
@@ -156,15 +156,7 @@ __device__ __forceinline__ uint32_t bf16_trunc_bits(float v) { return __float_as
 // (a >> 16) | (b & 0xFFFF0000): the bf16 truncations of a and b as one packed pair, a in the low half
 __device__ __forceinline__ uint32_t upper_halves(float a, float b) { return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u); }
 
-// The sum of the MLP weight-gradient partials of the PREVIOUS step + Adam on the small parameters (what nadm_small_grads does
-// as a launch of its own: 4.7 us + a launch gap at the end of every step) as side blocks of pass 1: pass 1 reads none of the
-// small parameters, the MLP forward behind it reads all of them.  part == nullptr: no side blocks.
-struct SmallSide {
-    const float* part;
-    float *out, *p, *m, *v;
-    int splits, n;
-    float step_size, inv_bc2, grad_scale;
-};
+// (SmallSide, the side blocks of the matrix-core pass 1: nadm_pass_args.h)
 
 // block id -> work item such that the blocks the dispatcher places on one XCD (id % 8) get consecutive items
 __device__ __forceinline__ int64_t xcd_chunk(const unsigned bid, const unsigned nwg) {
@@ -589,18 +581,7 @@ __global__ __launch_bounds__(256) void encode_bwd_kernel(
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Shape of the bf16 matrix-core pass-2 kernel (KP <= 8), tuned on MI355X with bench.py (b=800, M=500k, K=8; decode time
-// with / without the loss):  8 waves x 4 tiles, occupancy 2: 435 / 373 us;  8 x 2, occ. 4: 401 / 331;  4 x 2, occ. 4:
-// 400 / 334;  4 waves x 4 tiles at <= 168 VGPRs (3 blocks = 3 waves per SIMD, 42 KB LDS each): 388 / 310  <- default.
-#ifndef NADM_BF_WAVES
-#define NADM_BF_WAVES 4      // waves per block; chunk = WAVES * NTW * 16 SNPs
-#endif
-#ifndef NADM_BF_NTW
-#define NADM_BF_NTW 4        // 16-SNP tiles per wave (2 or 4)
-#endif
-#ifndef NADM_BF_TS
-#define NADM_BF_TS 64        // samples per LDS tile
-#endif
+// (the shape of the bf16 matrix-core pass-2 kernel, NADM_BF_WAVES / _NTW / _TS, and its chunking mf_chunk_snps: nadm_pass_args.h)
 #ifndef NADM_BF_WPE
 #define NADM_BF_WPE 3        // waves per SIMD the register allocator must leave room for (K <= 8)
 #endif
@@ -608,10 +589,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define NADM_BF_WPE_W 2      // ... for K 9..16: 7 MFMAs per tile and three more resident operands want 218 VGPRs; at 168 (3 waves) the
 #endif                       // kernel ran 721 us (K = 16, M = 1M), at 2 waves per SIMD 652, and 629 with the pair-product loss (r03)
 constexpr int bf_wpe(int kp) { return kp > 8 ? NADM_BF_WPE_W : NADM_BF_WPE; }
-constexpr int mf_waves(int kp) { return NADM_BF_WAVES; }   // waves per block
 constexpr int MF_RS_PAD = 16;       // LDS row stride of the X tile = row bytes + 16 (16 B aligned, de-phased banks)
-constexpr int mf_ntw(int kp) { return NADM_BF_NTW; }            // 16-SNP tiles per wave
-constexpr int mf_chunk_snps(int kp) { return mf_waves(kp) * 16 * mf_ntw(kp); }
 
 // =================================================================================================
 // pass 2, bf16 matrix-core version (KP <= 8).  f32-input MFMA runs on the vector ALUs and does not overlap
@@ -741,8 +719,7 @@ __device__ __forceinline__ void bce_loss_prod2(const f32x2_t d, const f32x2_t x,
 // missing calls (code 3) -> 0 in all 16 codes of a word: the model's input (neural_admixture.py:170)
 __device__ __forceinline__ uint32_t clean_codes(uint32_t w) { return w & ~((w & (w >> 1) & 0x55555555u) * 3u); }
 // the batch copy pass 2 leaves for pass 3 (nadm_decode_bce_gather): byte `col` of batch row `row` lives in tile col / 128 of
-// [b rows][128 bytes]
-constexpr int XG_TILE_COLS = 128;
+// [b rows][128 bytes] (XG_TILE_COLS, nadm_pass_args.h)
 __device__ __forceinline__ uint8_t* xg_piece(uint8_t* xg, int b, int row, int64_t col) {
     return xg + (col / XG_TILE_COLS) * ((int64_t)b * XG_TILE_COLS) + (int64_t)row * XG_TILE_COLS + (col % XG_TILE_COLS);
 }
@@ -759,9 +736,6 @@ __device__ __forceinline__ f32x2_t fp4_pair(const uint32_t w, const int sel) {
 }
 
 constexpr int BF_WAVES = NADM_BF_WAVES;
-// floats one (sample slice, SNP chunk) block of pass 2 parks for the block that adds the slices up: the chunk's [SNPs x KP] partial of dP +
-// its loss partial (+ 3 pad)
-constexpr int p2_slab_floats(int kp) { return NADM_BF_WAVES * 16 * NADM_BF_NTW * kp + 4; }
 constexpr int BF_NTW = NADM_BF_NTW;     // 16-SNP tiles per wave
 constexpr int BF_TS = NADM_BF_TS;       // samples per LDS tile
 
@@ -1309,9 +1283,7 @@ struct MlpSide {               // small_part == nullptr: no side work
     const float *Zn, *H, *dL, *dHpre, *dgp;
     float* small_part;
 };
-constexpr int EB_G = 2;                   // groups of 16 byte columns (64 SNPs) per wave
-constexpr int EB_COLS = 4 * EB_G * 16;    // packed byte columns per block (128)
-constexpr int EB_CHUNK_SNPS = EB_COLS * 4;
+// (EB_G, EB_COLS, EB_CHUNK_SNPS and p3_slab_floats, the chunking of the FP4 x FP6 pass 3: nadm_pass_args.h)
 
 // =================================================================================================
 // pass 3 on the FP4 x FP6 matrix instruction (CP <= 8, r03): dV = X^T . dZ on v_mfma_scale_f32_16x16x128_f8f6f4.
@@ -1347,8 +1319,6 @@ __global__ __launch_bounds__(256) void dz_image_kernel(const float* __restrict__
 constexpr int EB4_XS = 132;               // bytes per byte column of the LDS tile: 128 samples + 4 (dword stride 33: the loader's 4-byte
                                           // stores of 32 consecutive column quads and the 4-byte column reads spread over the banks)
 // CLEAN_SRC: xp is pass 2's copy of the batch (xg_piece: tiled by this kernel's chunks, rows in batch order, missing calls already 0)
-// floats one (sample slice, SNP chunk) block of pass 3 parks for the block that adds the slices up: the chunk's [512 SNPs x CP] partial of dV
-constexpr int p3_slab_floats(int cp) { return EB_CHUNK_SNPS * cp; }
 
 // SLICED (r06): S sample slices.  The grid is one block per 512-SNP chunk with the batch's 128-sample tiles as a loop inside:
 // a rank of the SNP-sharded mode (6400 rows x 62.5k SNPs at configs[3] on 8 GPUs) launches 122 blocks on 256 CUs and runs 75 us where the
@@ -1577,9 +1547,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
 }
 
-// ---- SNPs per lane in pass 2 as a function of the padded head width (register budget ~128) ----
-constexpr int dec_spl(int kp) { return kp <= 8 ? 8 : (kp <= 16 ? 4 : (kp <= 32 ? 2 : 1)); }
-
 // Adam on n floats for the variants of passes 2 and 3 that have no fused epilogue (same element function)
 __global__ __launch_bounds__(256) void adam_range_kernel(float* __restrict__ p, const float* __restrict__ g, AdamFused ad, int64_t n, int clamp01) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
@@ -1619,94 +1586,57 @@ static int launch_gather_rows(const uint8_t* xp, int64_t ld, const int32_t* idx,
 static std::atomic<unsigned long long*> g_clock_probe{nullptr};
 extern "C" void nadm_clock_probe(uint64_t* out2_dev) { g_clock_probe.store(reinterpret_cast<unsigned long long*>(out2_dev)); }
 
+// =================================================================================================
+// The launchers: one per launch struct (nadm_pass_args.h).  The host unit (nadm_passes_host.cpp) has checked the arguments and decided
+// the form; here the struct's run-time values become template arguments and the kernels are launched.
+// =================================================================================================
 template <int KP>
-static int launch_decode_mfma(const uint8_t* xp, int64_t ld, const int32_t* idx, int b, int64_t M, float* P,
-                              const float* Q, int SP, float* dP, float* dqpart, float* losspart, int with_loss,
-                              hipStream_t st, uint8_t* xg, AdamFused ad, const uint4* qimg, int n_slices, float* slab, int* slice_cnt,
-                              bool medium = false) {
+static int launch_decode_mfma(const Pass2Launch& a, hipStream_t st) {
     static_assert(KP <= 16 && mf_chunk_snps(KP) == BF_WAVES * 16 * BF_NTW, "chunking published by nadm_decode_chunk_snps");
-    const int64_t chunks = (M + mf_chunk_snps(KP) - 1) / mf_chunk_snps(KP);
-    dim3 grid((unsigned)chunks, (unsigned)n_slices), block(64 * BF_WAVES);
-    constexpr bool CAN_IMG = BF_TS == QI_TS;                 // (variant builds with another tile depth: decode_bce_impl refuses qimg)
-    unsigned long long* const clk_probe = g_clock_probe.load();
-    if (medium) {               // precision "medium": the Q-image forms only (decode_bce_impl refuses the rest), no probe twin
-#define NADM_P2_LAUNCH_MED(...)                                                                                                                 \
-    do {                                                                                                                                       \
-        if (n_slices > 1)                                                                                                                      \
-            hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, __VA_ARGS__, CAN_IMG, true, false, true>), grid, block, 0, st, xp, ld, idx, b, M, P, \
-                               Q, SP, dP, dqpart, losspart, xg, ad, qimg, slab, slice_cnt, (unsigned long long*)nullptr);                     \
-        else                                                                                                                                   \
-            hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, __VA_ARGS__, CAN_IMG, false, false, true>), grid, block, 0, st, xp, ld, idx, b, M, \
-                               P, Q, SP, dP, dqpart, losspart, xg, ad, qimg, slab, slice_cnt, (unsigned long long*)nullptr);                  \
-    } while (0)
-        if constexpr (CAN_IMG) {
-            if (with_loss & 2) NADM_P2_LAUNCH_MED(true, false);
-            else if (with_loss) NADM_P2_LAUNCH_MED(true, true);
-            else NADM_P2_LAUNCH_MED(false, true);
-        }
-#undef NADM_P2_LAUNCH_MED
-        return check_launch("decode_bce_bf16 (medium)");
-    }
-#define NADM_P2_LAUNCH(...)                                                                                                                     \
-    do {                                                                                                                                       \
-        if (n_slices > 1)                                                                                                                      \
-            hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, __VA_ARGS__, true>), grid, block, 0, st, xp, ld, idx, b, M, P, Q, SP, dP, dqpart,   \
-                               losspart, xg, ad, qimg, slab, slice_cnt, (unsigned long long*)nullptr);                                        \
-        else if (clk_probe != nullptr)                                                                                                         \
-            hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, __VA_ARGS__, false, true>), grid, block, 0, st, xp, ld, idx, b, M, P, Q, SP, dP,    \
-                               dqpart, losspart, xg, ad, qimg, slab, slice_cnt, clk_probe);                                                    \
-        else                                                                                                                                   \
-            hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, __VA_ARGS__, false>), grid, block, 0, st, xp, ld, idx, b, M, P, Q, SP, dP, dqpart,  \
-                               losspart, xg, ad, qimg, slab, slice_cnt, (unsigned long long*)nullptr);                                        \
-    } while (0)
-    if (with_loss & 2) {        // loss value with P possibly outside [0, 1] (before the first restrict_P)
-        if (qimg) NADM_P2_LAUNCH(true, false, CAN_IMG); else NADM_P2_LAUNCH(true, false, false);
-    } else if (with_loss) {
-        if (qimg) NADM_P2_LAUNCH(true, true, CAN_IMG); else NADM_P2_LAUNCH(true, true, false);
-    } else {
-        if (qimg) NADM_P2_LAUNCH(false, true, CAN_IMG); else NADM_P2_LAUNCH(false, true, false);
-    }
-#undef NADM_P2_LAUNCH
-    return check_launch("decode_bce_bf16");
+    const int64_t chunks = (a.M + mf_chunk_snps(KP) - 1) / mf_chunk_snps(KP);
+    dim3 grid((unsigned)chunks, (unsigned)a.n_slices), block(64 * BF_WAVES);
+    constexpr bool CAN_IMG = BF_TS == QI_TS;                 // (variant builds with another tile depth: pass2 refuses qimg)
+    // the probe twin exists for the S = 1 form of "highest" only; "medium" runs the Q-image forms only (pass2 refuses the rest)
+    unsigned long long* const clk_probe = (a.sliced || a.medium) ? nullptr : g_clock_probe.load();
+    dispatch_int<0, 1, 3>(a.loss ? (a.unit_p ? 1 : 3) : 0, [&](auto wl) {          // 3: the loss value with P possibly outside [0, 1]
+        constexpr bool LOSS = decltype(wl)::value != 0, UNIT_P = decltype(wl)::value != 3;
+        dispatch_bool([&](auto qi, auto sl, auto pr, auto md) {
+            constexpr bool QIMG = decltype(qi)::value, SLICED = decltype(sl)::value, PROBE = decltype(pr)::value, MED = decltype(md)::value;
+            if constexpr (!(PROBE && (SLICED || MED)) && !(MED && !QIMG))
+                hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, LOSS, UNIT_P, QIMG, SLICED, PROBE, MED>), grid, block, 0, st, a.xp, a.ld, a.idx, a.b, a.M,
+                                   a.P, a.Q, a.SP, a.dP, a.dqpart, a.losspart, a.xg, a.ad, static_cast<const uint4*>(a.qimg), a.slab, a.counters,
+                                   clk_probe);
+        }, CAN_IMG && a.qimg != nullptr, a.sliced, clk_probe != nullptr, a.medium);
+    });
+    return check_launch(a.medium ? "decode_bce_bf16 (medium)" : "decode_bce_bf16");
 }
 
 template <int KP>
-static int launch_decode(const uint8_t* xp, int64_t ld, const int32_t* idx, int b, int64_t M, float* P,
-                         const float* Q, int SP, float* dP, float* dqpart, float* losspart, int with_loss,
-                         hipStream_t st, uint8_t* xg, AdamFused ad) {
+static int launch_decode(const Pass2Launch& a, hipStream_t st) {
     constexpr int SPL = dec_spl(KP);
-    const int64_t chunks = (M + 256 * SPL - 1) / (256 * SPL);
+    const int64_t chunks = (a.M + 256 * SPL - 1) / (256 * SPL);
     dim3 grid((unsigned)chunks), block(256);
-    if (with_loss)
-        hipLaunchKernelGGL((decode_bce_kernel<KP, SPL, true>), grid, block, 0, st, xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart);
-    else
-        hipLaunchKernelGGL((decode_bce_kernel<KP, SPL, false>), grid, block, 0, st, xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart);
+    dispatch_bool([&](auto loss) {
+        hipLaunchKernelGGL((decode_bce_kernel<KP, SPL, decltype(loss)::value>), grid, block, 0, st, a.xp, a.ld, a.idx, a.b, a.M, a.P, a.Q, a.SP, a.dP,
+                           a.dqpart, a.losspart);
+    }, a.loss);
     if (check_launch("decode_bce")) return 1;
-    if (xg && launch_gather_rows(xp, ld, idx, b, M, xg, st)) return 1;
-    return ad.m ? launch_adam_range(P, dP, ad, M * KP, st, 1) : 0;
+    if (a.xg && launch_gather_rows(a.xp, a.ld, a.idx, a.b, a.M, a.xg, st)) return 1;
+    return a.ad.m ? launch_adam_range(a.P, a.dP, a.ad, a.M * KP, st, 1) : 0;
 }
 
-}  // namespace nadm
-
-using namespace nadm;
-
-// The matrix-core kernels of passes 1 and 3 cover CP <= 8; wider encoders (n_components > 8) run the VALU kernels.
-// The chunk count must not depend on CP (callers size zpart before they pass CP): both pass-1 kernels write 2048-SNP chunks.
-static_assert(ENC_TB * 4 * ENC_TILES == EM_CHUNK_SNPS, "one chunking for both pass-1 kernels");
-extern "C" int64_t nadm_encode_chunks(int64_t M) { return (M + EM_CHUNK_SNPS - 1) / EM_CHUNK_SNPS; }
-
-extern "C" int32_t nadm_decode_chunk_snps(int kp) {
-    if (kp <= 16) return mf_chunk_snps(kp);
-    return 256 * dec_spl(kp);
-}
-
-extern "C" int64_t nadm_decode_chunks(int64_t M, int kp) {
-    const int64_t c = nadm_decode_chunk_snps(kp);
-    return (M + c - 1) / c;
+int launch_pass2(const Pass2Launch& a) {
+    int rc = 0;
+    if (dispatch_kp("nadm_decode_bce", a.kp, [&](auto kp) {
+            constexpr int KP = decltype(kp)::value;
+            if constexpr (KP <= 16) rc = launch_decode_mfma<KP>(a, (hipStream_t)a.stream);
+            else rc = launch_decode<KP>(a, (hipStream_t)a.stream);
+        })) return 1;
+    return rc;
 }
 
 // compute units of the current device (cached per device ordinal; 256 if the runtime cannot say)
-static int device_cu_count() {
+int device_cu_count() {
     static int cached[64] = {0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -1724,413 +1654,64 @@ static int enc_rows_per_block(int b) {
     return ((per + 63) / 64) * 64;
 }
 
-static int encode_fwd_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                           const float* V, int32_t CP, float* zpart, void* stream, uint32_t missing_bf16,
-                           SmallSide ss = SmallSide{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0.f}, int64_t total_chunks = 0,
-                           bool medium = false) {
-    if (!xp || !idx || !V || !zpart) return fail("nadm_encode_fwd: null pointer");
-    if (b <= 0 || M <= 0) return fail("nadm_encode_fwd: empty batch or M");
-    if (ld % 16 != 0 || ld * 4 < M) return fail("nadm_encode_fwd: ld must be a multiple of 16 and >= ceil(M/4)");
-    if (ld >> 32) return fail("nadm_encode_fwd: rows of 4 GiB and more (ld >= 2^32) are not supported");      // the matrix pass forms row addresses from 32-bit factors
-    const int rpb = enc_rows_per_block(b);
-    dim3 grid((unsigned)nadm_encode_chunks(M), (unsigned)((b + rpb - 1) / rpb)), block(rpb);
-    const size_t lds = (size_t)rpb * ENC_LDW * 4;
-    hipStream_t st = (hipStream_t)stream;
-    if (CP <= 8) {
-        // Every block first splits its 2048 x CP slice of V into bf16 operands (about as much work as 11 sample tiles), so a block
-        // should see many tiles; but the 512 block slots of the chip (2 per CU) want to be filled, and a partly filled last round
-        // costs most of a full one.  grid.y = the number of batch splits (never fewer than 4 tiles per block) that minimises
-        //   rounds_eff(chunks * gy / slots) * (11.3 + tiles / gy),   slots = 2 blocks per CU of the device the launch goes to (512 on an
-        //   MI355X in SPX mode; a partition or another SKU reports its own CU count)
-        // with rounds_eff() read off measured launches (profiles/r03_p1_batch_splits.txt: b = 800, M = 500k .. 1M, grid.y = 1..4; the
-        // model reproduces all twenty within 2 us except one): a block alone on its CU runs 1.5 x faster, a round that is a
-        // little over-full costs 1.4 rounds.  M = 500k: 2 splits (43.6 us; 1 / 3 / 4: 49.1 / 47.7 / 49.0), 600k: 3 (56.1; 60.0 with
-        // the 2 that r02's rule "as few splits as give 480 blocks" picked), 800k: 1 (70.9; 73.3 with 2), 1M: 1 (73.6).
-        const int64_t chunks = nadm_encode_chunks(M);
-        const int ntiles = (b + 15) / 16;
-        auto rounds_eff = [](double x) {
-            if (x <= 0.5) return 0.67;
-            if (x <= 1.0) return 0.92 + 0.16 * (x - 0.5);
-            if (x <= 1.5) return 1.40;
-            if (x <= 1.95) return 1.70;
-            if (x <= 2.0) return 2.00;
-            return 0.45 + 0.72 * x;
-        };
-        const double slots = 2.0 * (double)device_cu_count();
-        // (a launch that is one PART of a pass shares the device with the other parts: the split is the whole pass's, nadm_encode_fwd_part)
-        const int64_t fill_chunks = total_chunks > chunks ? total_chunks : chunks;
-        int64_t gy = 1;
-        double best = 1e30;
-        for (int64_t g = 1; g <= 64 && g <= (ntiles + 3) / 4; ++g) {
-            const double cost = rounds_eff((double)(fill_chunks * g) / slots) * (11.3 + (double)((ntiles + g - 1) / g));
-            if (cost < best) { best = cost; gy = g; }
-        }
-        int tpb = (int)((ntiles + gy - 1) / gy);
-        if (tpb > EM_TILES_PER_BLOCK) tpb = EM_TILES_PER_BLOCK;
-        gy = (ntiles + tpb - 1) / tpb;
-        const int side_blocks = ss.part ? (ss.n + 511) / 512 : 0;
-        dim3 g2((unsigned)(chunks * gy + side_blocks)), b2(512);
-        if (medium) {          // precision "medium": V as hi + mid (the plan's step only)
-            if (CP == 4) hipLaunchKernelGGL((encode_fwd_mfma_kernel<4, true>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
-            else hipLaunchKernelGGL((encode_fwd_mfma_kernel<8, true>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
-        } else if (CP == 4) hipLaunchKernelGGL((encode_fwd_mfma_kernel<4>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
-        else hipLaunchKernelGGL((encode_fwd_mfma_kernel<8>), g2, b2, 0, st, xp, ld, idx, b, M, V, zpart, tpb, missing_bf16, (int)chunks, (int)gy, ss);
+static_assert(ENC_TB * 4 * ENC_TILES == EM_CHUNK_SNPS, "one chunking for both pass-1 kernels");
+int launch_pass1(const Pass1Launch& a) {
+    hipStream_t st = (hipStream_t)a.stream;
+    if (a.CP <= 8) {                                    // the matrix-core kernel: 1-D grid of chunks x batch splits, side blocks last
+        dim3 grid((unsigned)(a.chunks * a.gy + a.side_blocks)), block(512);
+        dispatch_bool([&](auto c4, auto med) {
+            hipLaunchKernelGGL((encode_fwd_mfma_kernel<decltype(c4)::value ? 4 : 8, decltype(med)::value>), grid, block, 0, st, a.xp, a.ld, a.idx, a.b,
+                               a.M, a.V, a.zpart, a.tpb, a.missing_bf16, (int)a.chunks, a.gy, a.ss);
+        }, a.CP == 4, a.medium);
         return check_launch("encode_fwd_mfma");
     }
-    if (ss.part) return fail("nadm_encode_fwd_small: only the matrix-core pass (CP <= 8) hosts the side blocks");
-#define ENC_LAUNCH(cp)                                                                                                 \
-    {                                                                                                                  \
-        if (lds > 48 * 1024) {                                                                                         \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_fwd_kernel<cp>),            \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-            if (e != hipSuccess) {                                                                                     \
-                snprintf(err_buf(), 512, "nadm_encode_fwd: cannot raise dynamic LDS limit to %zu: %s", lds,            \
-                         hipGetErrorString(e));                                                                        \
-                return 1;                                                                                              \
-            }                                                                                                          \
-        }                                                                                                              \
-        hipLaunchKernelGGL((encode_fwd_kernel<cp>), grid, block, lds, st, xp, ld, idx, b, M, V, zpart, rpb);           \
+    const int rpb = enc_rows_per_block(a.b);
+    dim3 grid((unsigned)a.chunks, (unsigned)((a.b + rpb - 1) / rpb)), block(rpb);
+    const size_t lds = (size_t)rpb * ENC_LDW * 4;
+    hipError_t e = hipSuccess;
+    dispatch_int<12, 16, 24, 32>(a.CP, [&](auto cp) {
+        constexpr int CP = decltype(cp)::value;
+        if (lds > 48 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_fwd_kernel<CP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) hipLaunchKernelGGL((encode_fwd_kernel<CP>), grid, block, lds, st, a.xp, a.ld, a.idx, a.b, a.M, a.V, a.zpart, rpb);
+    });
+    if (e != hipSuccess) {
+        snprintf(err_buf(), 512, "nadm_encode_fwd: cannot raise dynamic LDS limit to %zu: %s", lds, hipGetErrorString(e));
+        return 1;
     }
-#define ENC_CASE(cp)                                                                                                   \
-    case cp:                                                                                                           \
-        ENC_LAUNCH(cp)                                                                                                 \
-        break;
-    switch (CP) {
-        ENC_CASE(12) ENC_CASE(16) ENC_CASE(24) ENC_CASE(32)          // (CP 4, 8: the matrix-core kernel above)
-        default: return fail("nadm_encode_fwd: unsupported CP (4,8,12,16,24,32)");
-    }
-#undef ENC_LAUNCH
-#undef ENC_CASE
     return check_launch("encode_fwd");
 }
 
-static int adam_fused_args(const nadm_adam_t* adam, const char* who, AdamFused* out) {
-    *out = AdamFused{nullptr, nullptr, 0.f, 0.f, 0.f};
-    if (!adam) return 0;
-    if (!adam->m || !adam->v) return fail(who);
-    if (adam->step < 1) return fail("nadm_*_step: Adam step is 1-based");
-    if (((uintptr_t)adam->m | (uintptr_t)adam->v) & 15) return fail("nadm_*_step: Adam state must be 16-byte aligned");
-    out->m = adam->m; out->v = adam->v; out->grad_scale = adam->grad_scale;
-    if (adam->reserved != 0) return fail("nadm_*_step: nadm_adam_t.reserved must be 0");
-    adam_scalars(adam->lr, adam->step, &out->step_size, &out->inv_bc2);
-    return 0;
-}
-
-extern "C" int nadm_encode_fwd(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                               const float* V, int32_t CP, float* zpart, void* stream) {
-    return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0u);
-}
-
-extern "C" int nadm_encode_fwd_part(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                    const float* V, int32_t CP, float* zpart, int64_t total_chunks, void* stream) {
-    return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0u, SmallSide{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0.f}, total_chunks);
-}
-
-static int small_side_args(const float* small_part, int32_t splits, int32_t n_small, float* grad_small, float* small, const nadm_adam_t* adam,
-                           SmallSide* out) {
-    if (!small_part || !grad_small) return fail("nadm_encode_fwd_small: null pointer");
-    if (splits <= 0 || n_small <= 0) return fail("nadm_encode_fwd_small: empty");
-    SmallSide ss{small_part, grad_small, small, nullptr, nullptr, splits, n_small, 0.f, 0.f, 0.f};
-    if (adam) {
-        if (!adam->m || !adam->v || !small) return fail("nadm_encode_fwd_small: Adam state / parameters are NULL");
-        if (adam->step < 1) return fail("nadm_encode_fwd_small: Adam step is 1-based");
-        ss.m = adam->m; ss.v = adam->v; ss.grad_scale = adam->grad_scale;
-        adam_scalars(adam->lr, adam->step, &ss.step_size, &ss.inv_bc2);
-    }
-    *out = ss;
-    return 0;
-}
-
-extern "C" int nadm_encode_fwd_small(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                     const float* V, int32_t CP, float* zpart, const float* small_part, int32_t splits, int32_t n_small,
-                                     float* grad_small, float* small, const nadm_adam_t* adam, void* stream) {
-    SmallSide ss;
-    if (small_side_args(small_part, splits, n_small, grad_small, small, adam, &ss)) return 1;
-    return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0u, ss);
-}
-
-extern "C" int nadm_pca_project(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                const float* V, int32_t CP, float* zpart, void* stream) {
-    if (CP > 8) return fail("nadm_pca_project: only the matrix-core pass (CP <= 8) has the missing = 1.5 variant");
-    return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0x3FC0u);
-}
-
-// ---- sample slices, the host's side of slice_tiles (nadm_common.h), shared by passes 2 and 3: the n_slices argument of a pass, refused
-// in the entry point's own words (`no_kernel`: why this shape has no sliced kernel, or NULL)
-static int slice_args(int32_t n_slices, int tiles, const float* slab, const int32_t* counters, const char* out_of_range, const char* no_kernel,
-                      const char* no_slab, const char* empty_slice) {
-    if (n_slices < 1 || n_slices > NADM_MAX_P2_SLICES) return fail(out_of_range);
-    if (n_slices == 1) return 0;
-    if (no_kernel) return fail(no_kernel);
-    if (!slab || !counters || ((uintptr_t)slab & 15)) return fail(no_slab);
-    return slices_leave_one_empty(tiles, n_slices) ? fail(empty_slice) : 0;
-}
-// the most slices any batch of up to bmax rows is cut into: the rule of the pass at every tile count
-static int32_t slices_max(int32_t (*rule)(int32_t, int64_t, int32_t), int32_t bmax, int64_t M, int32_t width, int tile_rows) {
-    int32_t mx = 1;
-    for (int32_t b = bmax; b > 0; b -= tile_rows) { const int32_t s = rule(b, M, width); if (s > mx) mx = s; }
-    return mx;
-}
-
-static int decode_bce_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                           float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
-                           float* losspart, int32_t with_loss, void* stream, uint8_t* xg, AdamFused ad, const uint4* qimg = nullptr,
-                           int32_t n_slices = 1, float* slab = nullptr, int32_t* slice_cnt = nullptr, bool medium = false) {
-    if (!xp || !idx || !P || !Q || !dP || !dqpart) return fail("nadm_decode_bce: null pointer");
-    if (medium && kp <= 16 && (!qimg || NADM_BF_TS != nadm::QI_TS))        // (kp > 16: the VALU kernel, the same under either precision)
-        return fail("nadm_step: precision \"medium\" runs pass 2 from the Q images (nadm_plan_desc_t.qimg) at padded K <= 16");
-    if (ld >> 32) return fail("nadm_decode_bce: rows of 4 GiB and more (ld >= 2^32) are not supported");      // the matrix pass forms row addresses from 32-bit factors
-    if (slice_args(n_slices, (b + NADM_BF_TS - 1) / NADM_BF_TS, slab, slice_cnt, "nadm_decode_bce_sliced: n_slices must be in 1..8",
-                   kp > 16 ? "nadm_decode_bce_sliced: sample slices exist for padded K <= 16 only" : nullptr,
-                   "nadm_decode_bce_sliced: n_slices > 1 needs the slab (16-byte aligned) and the counters",
-                   "nadm_decode_bce_sliced: a slice would be empty (take n_slices from nadm_decode_slices)")) return 1;
-    if (qimg &&(kp > 16 || NADM_BF_TS != nadm::QI_TS)) return fail("nadm_decode_bce_images: Q images exist for padded K <= 16 only");
-    if ((uintptr_t)qimg & 15) return fail("nadm_decode_bce_images: qimg must be 16-byte aligned");
-    if (with_loss < 0 || with_loss > 3) return fail("nadm_decode_bce: with_loss is a bit set (1: loss value, 2: P may lie outside [0,1])");
-    if (!(with_loss & 1)) with_loss = 0;
-    if (with_loss && !losspart) return fail("nadm_decode_bce: with_loss needs losspart");
-    if (b <= 0 || M <= 0) return fail("nadm_decode_bce: empty batch or M");
-    if (ld % 16 != 0 || ld * 4 < M) return fail("nadm_decode_bce: ld must be a multiple of 16 and >= ceil(M/4)");
-    hipStream_t st = (hipStream_t)stream;
-    if (kp <= 16) {
-        switch (kp) {
-            case 4: return launch_decode_mfma<4>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt, medium);
-            case 8: return launch_decode_mfma<8>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt, medium);
-            case 12: return launch_decode_mfma<12>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt, medium);
-            case 16: return launch_decode_mfma<16>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad, qimg, n_slices, slab, slice_cnt, medium);
-            default: return fail("nadm_decode_bce: unsupported padded K (use nadm_pad_k)");
-        }
-    }
-    switch (kp) {
-        case 24: return launch_decode<24>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad);
-        case 32: return launch_decode<32>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad);
-        case 48: return launch_decode<48>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad);
-        case 64: return launch_decode<64>(xp, ld, idx, b, M, P, Q, SP, dP, dqpart, losspart, with_loss, st, xg, ad);
-        default: return fail("nadm_decode_bce: unsupported padded K (use nadm_pad_k)");
-    }
-}
-
-extern "C" int nadm_decode_bce(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                               const float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
-                               float* losspart, int32_t with_loss, void* stream) {
-    return decode_bce_impl(xp, ld, idx, b, M, const_cast<float*>(P), kp, Q, SP, dP, dqpart, losspart, with_loss, stream, nullptr, AdamFused{nullptr, nullptr, 0.f, 0.f, 0.f});
-}
-
-extern "C" int nadm_decode_bce_gather(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                      const float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
-                                      float* losspart, int32_t with_loss, uint8_t* xg, void* stream) {
-    if (!xg) return fail("nadm_decode_bce_gather: null pointer");
-    return decode_bce_impl(xp, ld, idx, b, M, const_cast<float*>(P), kp, Q, SP, dP, dqpart, losspart, with_loss, stream, xg, AdamFused{nullptr, nullptr, 0.f, 0.f, 0.f});
-}
-
-extern "C" int nadm_decode_bce_step(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                    float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
-                                    float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, void* stream) {
-    AdamFused ad;
-    if (adam_fused_args(adam, "nadm_decode_bce_step: Adam state is NULL", &ad)) return 1;
-    if ((uintptr_t)P & 15) return fail("nadm_decode_bce_step: P must be 16-byte aligned");
-    return decode_bce_impl(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, stream, xg, ad);
-}
-
-extern "C" int64_t nadm_q_image_bytes(int32_t b) { return (int64_t)((b + nadm::QI_TS - 1) / nadm::QI_TS) * nadm::QI_TILE_U4 * 16; }
-
-extern "C" int nadm_decode_bce_images(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                      float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
-                                      float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, const void* qimg,
-                                      void* stream) {
-    AdamFused ad;
-    if (adam_fused_args(adam, "nadm_decode_bce_images: Adam state is NULL", &ad)) return 1;
-    if (ad.m && ((uintptr_t)P & 15)) return fail("nadm_decode_bce_images: P must be 16-byte aligned");
-    if (!qimg) return fail("nadm_decode_bce_images: qimg is NULL (use nadm_decode_bce_step)");
-    return decode_bce_impl(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, stream, xg, ad, static_cast<const uint4*>(qimg));
-}
-
-// ---- pass 2 with the batch's sample tiles dealt to n_slices blocks per SNP chunk (see decode_bce_bf16_kernel)
-extern "C" int32_t nadm_decode_slices(int32_t b, int64_t M, int32_t kp) {
-    if (kp > 16 || b <= 0 || M <= 0) return 1;
-    const int64_t chunks = (M + mf_chunk_snps(8) - 1) / mf_chunk_snps(8);
-    const int tiles = (b + NADM_BF_TS - 1) / NADM_BF_TS;
-    int s = hook_p2_slices();                                       // 0 (always, in the shipping library): the rule below
-    if (s == 0) {
-        // Measured (profiles/r05_ablations.txt item 11): below ~130k SNPs pass 2 is bound by the serial chain of ONE block -- its prologue
-        // (P rows into operands, ~1.5 tile-times) + 13 tiles at b = 800 = 49 us whether 98 or 196 blocks run -- not by the chip; slices of
-        // ~4-5 tiles shorten the chain (M = 25k: 49 -> 32 us, 50k: 50 -> 43, 100k: 73.5 -> 66.5; 6400 rows x 62.5k SNPs, the SNP-sharded
-        // rank of configs[3]: 326 -> 244).  A slice costs a prologue and the launch ~5 us for the hand-off: short batches (< 8 tiles: b = 400
-        // at M = 100k 44.4 -> 45.3, b = 200 at 50k 20.9 -> 23.6) and launches of more than ~1.7 rounds of blocks do not pay; from 150k SNPs
-        // on the chunks fill the chip and nothing changes.
-        if (chunks >= 512 || tiles < 8) return 1;
-        s = (int)((2 * tiles + 4) / 9);                             // round(tiles / 4.5)
-        const int64_t lim = 1280 / chunks;                           // blocks <= 1280 = 1.7 rounds of 768
-        if (s > lim) s = (int)lim;
-        if (s > NADM_MAX_P2_SLICES) s = NADM_MAX_P2_SLICES;
-    }
-    return slices_without_empty(tiles, s);
-}
-
-extern "C" int32_t nadm_decode_slices_max(int32_t bmax, int64_t M, int32_t kp) { return slices_max(nadm_decode_slices, bmax, M, kp, NADM_BF_TS); }
-
-extern "C" int64_t nadm_decode_slab_floats(int64_t M, int32_t kp, int32_t n_slices) {
-    if (kp > 16 || n_slices < 2 || M <= 0) return 0;
-    return (int64_t)n_slices * ((M + mf_chunk_snps(8) - 1) / mf_chunk_snps(8)) * p2_slab_floats(kp);
-}
-
-extern "C" int nadm_decode_bce_sliced(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                      float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
-                                      float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, const void* qimg,
-                                      int32_t n_slices, float* slab, int32_t* counters, void* stream) {
-    AdamFused ad;
-    if (adam_fused_args(adam, "nadm_decode_bce_sliced: Adam state is NULL", &ad)) return 1;
-    if (ad.m && ((uintptr_t)P & 15)) return fail("nadm_decode_bce_sliced: P must be 16-byte aligned");
-    return decode_bce_impl(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, stream, xg, ad, static_cast<const uint4*>(qimg),
-                           n_slices, slab, counters);
-}
-
-// ---- the plan's step with its matmul precision (nadm_host.h)
-int nadm::decode_bce_prec(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, float* P, int32_t kp, const float* Q, int32_t SP,
-                          float* dP, float* dqpart, float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, const void* qimg,
-                          int32_t n_slices, float* slab, int32_t* counters, int32_t precision, void* stream) {
-    if (precision != NADM_PRECISION_MEDIUM) {                       // exactly the public forms
-        if (n_slices > 1)
-            return nadm_decode_bce_sliced(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, adam, qimg, n_slices, slab, counters, stream);
-        if (qimg) return nadm_decode_bce_images(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, adam, qimg, stream);
-        return nadm_decode_bce_step(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, adam, stream);
-    }
-    AdamFused ad;
-    if (adam_fused_args(adam, "nadm_step: Adam state is NULL", &ad)) return 1;
-    if (ad.m && ((uintptr_t)P & 15)) return fail("nadm_step: P must be 16-byte aligned");
-    return decode_bce_impl(xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, stream, xg, ad, static_cast<const uint4*>(qimg),
-                           n_slices, slab, counters, true);
-}
-
-int nadm::encode_fwd_prec(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* V, int32_t CP, float* zpart,
-                          int64_t total_chunks, const float* small_part, int32_t splits, int32_t n_small, float* grad_small, float* small,
-                          const nadm_adam_t* adam, int32_t precision, void* stream) {
-    if (precision != NADM_PRECISION_MEDIUM) {                       // exactly the public forms
-        if (small_part) return nadm_encode_fwd_small(xp, ld, idx, b, M, V, CP, zpart, small_part, splits, n_small, grad_small, small, adam, stream);
-        if (total_chunks > 0) return nadm_encode_fwd_part(xp, ld, idx, b, M, V, CP, zpart, total_chunks, stream);
-        return nadm_encode_fwd(xp, ld, idx, b, M, V, CP, zpart, stream);
-    }
-    SmallSide ss{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0.f};
-    if (small_part && small_side_args(small_part, splits, n_small, grad_small, small, adam, &ss)) return 1;
-    return encode_fwd_impl(xp, ld, idx, b, M, V, CP, zpart, stream, 0u, ss, total_chunks, CP <= 8);
-}
-
-extern "C" int64_t nadm_batch_copy_bytes(int32_t b, int64_t M) { return ((M + 4 * nadm::XG_TILE_COLS - 1) / (4 * nadm::XG_TILE_COLS)) * (int64_t)b * nadm::XG_TILE_COLS; }
-extern "C" int64_t nadm_dz_image_tile_bytes(void) { return (int64_t)nadm::DZI_TILE_U4 * 16; }
-extern "C" int64_t nadm_dz_image_bytes(int32_t b) { return (int64_t)((b + nadm::DZI_TS - 1) / nadm::DZI_TS) * nadm::DZI_TILE_U4 * 16; }
-
-extern "C" int nadm_dz_image(const float* dZ, int32_t b, int32_t CP, void* dzimg, void* stream) {
-    if (!dZ || !dzimg) return fail("nadm_dz_image: null pointer");
-    if (b <= 0 || CP <= 0 || CP > 8) return fail("nadm_dz_image: b > 0 and 0 < CP <= 8 (the matrix-core pass 3)");
-    if ((uintptr_t)dzimg & 15) return fail("nadm_dz_image: the image must be 16-byte aligned");
+int launch_dz_image(const float* dZ, int32_t b, int32_t CP, void* dzimg, void* stream) {
     hipLaunchKernelGGL(dz_image_kernel, dim3((unsigned)((b + DZI_TS - 1) / DZI_TS)), dim3(256), 0, (hipStream_t)stream, dZ, b, CP, (uint4*)dzimg);
     return check_launch("dz_image");
 }
 
-static int encode_bwd_impl(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                           const float* dZ, const void* dzimg, int32_t CP, float* dV, void* stream, uint32_t missing_bf16, int32_t flags = 0,
-                           float* Vrw = nullptr, AdamFused ad = AdamFused{nullptr, nullptr, 0.f, 0.f, 0.f},
-                           const nadm_mlp_weights_t* mw = nullptr, int32_t n_slices = 1, float* slab = nullptr, int32_t* counters = nullptr) {
-    if (!xp || !idx || !dZ || !dV) return fail("nadm_encode_bwd: null pointer");
-    if (CP > 8 && (flags & NADM_X_CLEAN)) return fail("nadm_encode_bwd: the batch copy (NADM_X_CLEAN) is tiled for the matrix-core pass, C <= 8");
-    if (CP <= 8 && (!dzimg || ((uintptr_t)dzimg & 15)))
-        return fail("nadm_encode_bwd: C <= 8 runs on the FP4 x FP6 matrix instruction and needs the operand image of dZ (nadm_dz_image), 16-byte aligned");
-    if (b <= 0 || M <= 0) return fail("nadm_encode_bwd: empty batch or M");
-    if (ld % 16 != 0 || ld * 4 < M) return fail("nadm_encode_bwd: ld must be a multiple of 16 and >= ceil(M/4)");
-    dim3 grid((unsigned)((M + 1023) / 1024)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (CP <= 8) {
+int launch_pass3(const Pass3Launch& a) {
+    hipStream_t st = (hipStream_t)a.stream;
+    const nadm_mlp_weights_t* mw = a.weights;
+    if (a.CP <= 8) {
         MlpSide side;
         memset(&side, 0, sizeof(side));
         int64_t extra = 0;
         if (mw) {
-            side.hd = *mw->hd; side.b = b; side.gx = (mw->hd->Hd + 255) / 256;
+            side.hd = *mw->hd; side.b = a.b; side.gx = (mw->hd->Hd + 255) / 256;
             side.Zn = mw->Zn; side.H = mw->H; side.dL = mw->dL; side.dHpre = mw->dHpre; side.dgp = mw->dgp; side.small_part = mw->small_part;
-            extra = (int64_t)side.gx * nadm_sample_splits(b);
+            extra = (int64_t)side.gx * nadm_sample_splits(a.b);
         }
-        if (slice_args(n_slices, (b + DZI_TS - 1) / DZI_TS, slab, counters, "nadm_encode_bwd_sliced: n_slices must be in 1..8", nullptr,
-                       "nadm_encode_bwd_sliced: the slab (16-byte aligned) and the counters are NULL",
-                       "nadm_encode_bwd_sliced: an empty sample slice")) return 1;
-        dim3 g2((unsigned)(((M + EB_CHUNK_SNPS - 1) / EB_CHUNK_SNPS) * n_slices + extra));
-#define NADM_P3_LAUNCH(CPV, CL, SL) hipLaunchKernelGGL((encode_bwd_fp4_kernel<CPV, CL, SL>), g2, block, 0, st, xp, ld, idx, b, M, (const uint4*)dzimg, dV, missing_bf16, Vrw, ad, side, slab, counters, (int)n_slices)
-        const bool clean = (flags & NADM_X_CLEAN) != 0 && missing_bf16 == 0u;
-        if (n_slices > 1) {
-            if (CP == 4) { if (clean) NADM_P3_LAUNCH(4, true, true); else NADM_P3_LAUNCH(4, false, true); }
-            else { if (clean) NADM_P3_LAUNCH(8, true, true); else NADM_P3_LAUNCH(8, false, true); }
-        } else if (CP == 4) { if (clean) NADM_P3_LAUNCH(4, true, false); else NADM_P3_LAUNCH(4, false, false); }
-        else { if (clean) NADM_P3_LAUNCH(8, true, false); else NADM_P3_LAUNCH(8, false, false); }
-#undef NADM_P3_LAUNCH
+        dim3 grid((unsigned)(((a.M + EB_CHUNK_SNPS - 1) / EB_CHUNK_SNPS) * a.n_slices + extra)), block(256);
+        dispatch_bool([&](auto c4, auto clean, auto sliced) {
+            hipLaunchKernelGGL((encode_bwd_fp4_kernel<decltype(c4)::value ? 4 : 8, decltype(clean)::value, decltype(sliced)::value>), grid, block, 0, st,
+                               a.xp, a.ld, a.idx, a.b, a.M, (const uint4*)a.dzimg, a.dV, a.missing_bf16, a.V, a.ad, side, a.slab, a.counters, (int)a.n_slices);
+        }, a.CP == 4, a.clean, a.sliced);
         return check_launch("encode_bwd_fp4");
     }
-    switch (CP) {
-        case 12: hipLaunchKernelGGL((encode_bwd_kernel<12>), grid, block, 0, st, xp, ld, idx, b, M, dZ, dV); break;
-        case 16: hipLaunchKernelGGL((encode_bwd_kernel<16>), grid, block, 0, st, xp, ld, idx, b, M, dZ, dV); break;
-        case 24: hipLaunchKernelGGL((encode_bwd_kernel<24>), grid, block, 0, st, xp, ld, idx, b, M, dZ, dV); break;
-        case 32: hipLaunchKernelGGL((encode_bwd_kernel<32>), grid, block, 0, st, xp, ld, idx, b, M, dZ, dV); break;
-        default: return fail("nadm_encode_bwd: unsupported CP (4,8,12,16,24,32)");
-    }
+    dim3 grid((unsigned)((a.M + 1023) / 1024)), block(256);
+    dispatch_int<12, 16, 24, 32>(a.CP, [&](auto cp) {
+        hipLaunchKernelGGL((encode_bwd_kernel<decltype(cp)::value>), grid, block, 0, st, a.xp, a.ld, a.idx, a.b, a.M, a.dZ, a.dV);
+    });
     if (check_launch("encode_bwd")) return 1;
-    if (ad.m && launch_adam_range(Vrw, dV, ad, M * CP, st, 0)) return 1;  // fp32 variants of pass 3: stand-alone update
-    return mw ? mlp_bwd_weight_parts(mw->hd, b, mw->Zn, mw->H, mw->dL, mw->dHpre, mw->dgp, mw->small_part, stream) : 0;
+    if (a.ad.m && launch_adam_range(a.V, a.dV, a.ad, a.M * a.CP, st, 0)) return 1;  // fp32 variants of pass 3: stand-alone update
+    return mw ? mlp_bwd_weight_parts(mw->hd, a.b, mw->Zn, mw->H, mw->dL, mw->dHpre, mw->dgp, mw->small_part, a.stream) : 0;
 }
 
-extern "C" int nadm_encode_bwd_step(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                    const float* dZ, const void* dzimg, int32_t CP, float* V, float* dV, const nadm_adam_t* adam,
-                                    const nadm_mlp_weights_t* weights, int32_t flags, void* stream) {
-    AdamFused ad;
-    if (adam_fused_args(adam, "nadm_encode_bwd_step: Adam state is NULL", &ad)) return 1;
-    if (ad.m && (!V || ((uintptr_t)V & 15))) return fail("nadm_encode_bwd_step: V must be non-NULL and 16-byte aligned");
-    if (weights && (!weights->hd || !weights->Zn || !weights->H || !weights->dL || !weights->dHpre || !weights->dgp || !weights->small_part))
-        return fail("nadm_encode_bwd_step: null pointer in the MLP weight-gradient arguments");
-    return encode_bwd_impl(xp, ld, idx, b, M, dZ, dzimg, CP, dV, stream, 0u, flags, V, ad, weights);
-}
-
-// ---- pass 3 with the batch's 128-sample tiles dealt to n_slices blocks per SNP chunk (see encode_bwd_fp4_kernel)
-extern "C" int32_t nadm_encode_slices(int32_t b, int64_t M, int32_t cp) {
-    if (cp > 8 || b <= 0 || M <= 0) return 1;
-    const int64_t chunks = (M + EB_CHUNK_SNPS - 1) / EB_CHUNK_SNPS;
-    const int tiles = (b + DZI_TS - 1) / DZI_TS;
-    int s = hook_p3_slices();                                       // 0 (always, in the shipping library): the rule below
-    if (s == 0) {
-        // Measured (profiles/r06_p3_slices.txt): a launch of ~120 chunk blocks that each walk 50 tiles (6400 rows x 62.5k SNPs, the SNP-sharded
-        // rank of configs[3] on 8 GPUs) lasts as long as one block's chain, 77 us where the same genotypes as 977 blocks take 41; two slices
-        // 57 us, three 62, four 64, eight 76 -- every slice pays a prologue and the hand-off (park 16 KB through to memory, be counted, the
-        // last one reads them all back and runs Adam: ~8 us of tail).  At 3200 x 125k (245 chunks x 25 tiles, 46 us) any cut loses: 53 / 65.
-        // So: two slices, only for few chunks AND long chains; every single-GPU BASELINE shape stays whole.
-        if (chunks >= 192 || tiles < 32) return 1;
-        s = 2;
-    }
-    return slices_without_empty(tiles, s);
-}
-
-extern "C" int32_t nadm_encode_slices_max(int32_t bmax, int64_t M, int32_t cp) { return slices_max(nadm_encode_slices, bmax, M, cp, DZI_TS); }
-
-extern "C" int64_t nadm_encode_slab_floats(int64_t M, int32_t cp, int32_t n_slices) {
-    if (cp > 8 || n_slices < 2 || M <= 0) return 0;
-    return (int64_t)n_slices * ((M + EB_CHUNK_SNPS - 1) / EB_CHUNK_SNPS) * p3_slab_floats(cp);
-}
-
-extern "C" int64_t nadm_encode_bwd_chunks(int64_t M) { return (M + EB_CHUNK_SNPS - 1) / EB_CHUNK_SNPS; }
-
-extern "C" int nadm_encode_bwd_sliced(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                      const float* dZ, const void* dzimg, int32_t CP, float* V, float* dV, const nadm_adam_t* adam,
-                                      const nadm_mlp_weights_t* weights, int32_t flags, int32_t n_slices, float* slab, int32_t* counters, void* stream) {
-    AdamFused ad;
-    if (adam_fused_args(adam, "nadm_encode_bwd_sliced: Adam state is NULL", &ad)) return 1;
-    if (ad.m && (!V || ((uintptr_t)V & 15))) return fail("nadm_encode_bwd_sliced: V must be non-NULL and 16-byte aligned");
-    if (CP > 8) return fail("nadm_encode_bwd_sliced: the matrix-core pass only (C <= 8)");
-    if (weights && (!weights->hd || !weights->Zn || !weights->H || !weights->dL || !weights->dHpre || !weights->dgp || !weights->small_part))
-        return fail("nadm_encode_bwd_sliced: null pointer in the MLP weight-gradient arguments");
-    return encode_bwd_impl(xp, ld, idx, b, M, dZ, dzimg, CP, dV, stream, 0u, flags, V, ad, weights, n_slices, slab, counters);
-}
-
-extern "C" int nadm_encode_bwd(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                               const float* dZ, const void* dzimg, int32_t CP, float* dV, int32_t flags, void* stream) {
-    return encode_bwd_impl(xp, ld, idx, b, M, dZ, dzimg, CP, dV, stream, 0u, flags);
-}
-
-extern "C" int nadm_pca_project_t(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
-                                  const float* Y, const void* yimg, int32_t CP, float* out, void* stream) {
-    if (CP > 8) return fail("nadm_pca_project_t: only the matrix-core pass (CP <= 8) has the missing = 1.5 variant");
-    return encode_bwd_impl(xp, ld, idx, b, M, Y, yimg, CP, out, stream, 0x3FC0u);
-}
+}  // namespace nadm

@@ -1,8 +1,8 @@
-// The test hooks: process-wide switches that override a launch rule of the kernel units (nadm_decode_slices, nadm_encode_slices, the
-// two MLP dispatches read them through the getters below).  This is the only unit that sees NADM_TEST_HOOKS: csrc/build.sh compiles it
+// The test hooks: process-wide switches that override a launch rule of the passes' host unit (nadm_decode_slices, nadm_encode_slices, the
+// choice of the MLP kernels read them through the getters below).  This is the only unit that sees NADM_TEST_HOOKS: csrc/build.sh compiles it
 // without the macro for libnadm.so -- no setter exists, every getter returns 0 -- and with it for libnadm_testhooks.so, which the
 // tests that need a hook load in a child process (tests/conftest.py: in_hook_build).  Both libraries link the same kernel objects.
-#include "nadm_host.h"
+#include "nadm_host_rules.h"
 
 #ifdef NADM_TEST_HOOKS
 #include <atomic>

@@ -1,8 +1,7 @@
-// Host-side helpers shared by the C-ABI translation units.
+// nadm_host_rules.h + what needs the HIP runtime: for the units that launch kernels.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <type_traits>
-#include "nadm_err.h"
+#include "nadm_host_rules.h"
 
 namespace nadm {
 
@@ -14,92 +13,5 @@ inline int check_launch(const char* what) {
     }
     return 0;
 }
-
-// ---- argument checks shared by the entry points that read the packed matrix and one head's Q and P.  Each sets the message
-// "<who>: <what>" and returns 1, or returns 0
-inline int failf(const char* who, const char* what) {
-    snprintf(err_buf(), 512, "%s: %s", who, what);
-    return 1;
-}
-inline int check_packed(const char* who, int64_t ld, int64_t M) {
-    if (ld * 4 < M) return failf(who, "ld < ceil(M/4)");
-    if (ld % 16 != 0 || ld >= (1ll << 32)) return failf(who, "ld must be a multiple of 16 and < 2^32");
-    return 0;
-}
-inline int check_head(const char* who, int32_t k, int32_t kp, int32_t q_stride) {
-    if (k < 1 || k > NADM_MAX_K) return failf(who, "K must be in 1..NADM_MAX_K");
-    if (kp != nadm_pad_k(k)) return failf(who, "kp must be nadm_pad_k(k)");
-    if (q_stride < kp) return failf(who, "q_stride < kp");
-    if (q_stride % 4 != 0) return failf(who, "q_stride must be a multiple of 4");
-    return 0;
-}
-inline int check_eps(const char* who, float eps) {
-    return (eps >= 1e-9f && eps < 0.5f) ? 0 : failf(who, "eps must be in [1e-9, 0.5)");
-}
-
-// f(std::integral_constant<int, KP>{}) for kp = KP, one of the eight padded widths of a head (nadm_pad_k)
-template <class F>
-inline int dispatch_kp(const char* who, int kp, F&& f) {
-    switch (kp) {
-        case 4: f(std::integral_constant<int, 4>{}); return 0;
-        case 8: f(std::integral_constant<int, 8>{}); return 0;
-        case 12: f(std::integral_constant<int, 12>{}); return 0;
-        case 16: f(std::integral_constant<int, 16>{}); return 0;
-        case 24: f(std::integral_constant<int, 24>{}); return 0;
-        case 32: f(std::integral_constant<int, 32>{}); return 0;
-        case 48: f(std::integral_constant<int, 48>{}); return 0;
-        case 64: f(std::integral_constant<int, 64>{}); return 0;
-        default: return failf(who, "unsupported padded K (use nadm_pad_k)");
-    }
-}
-
-// ---- the split rule of the kernels that cut one axis of their work into parts whose partial sums a second launch folds: the axis of
-// `units` units (tiles of samples, chunks of SNPs) is cut into as many parts as it takes to put `want_blocks` blocks on the chip, given
-// the `other` axis' block count, while there are units to split, and never more than `max_units` units go into one part (what one fp32
-// running sum may cover).  A rule of the shape alone.  Returns the units per part; the parts are ceil(units / that).
-inline int64_t split_per_part(int64_t units, int64_t other, int64_t want_blocks, int64_t max_units) {
-    int64_t want = (want_blocks + other - 1) / other;
-    if (want > units) want = units;
-    const int64_t least = (units + max_units - 1) / max_units;
-    if (want < least) want = least;
-    return (units + want - 1) / want;
-}
-// a bound of parts x other for sizing the partials that grows with units and with other (the product itself does not:
-// ceil(want_blocks / other) other wobbles with other)
-inline int64_t split_blocks_bound(int64_t units, int64_t other, int64_t want_blocks, int64_t max_units) {
-    const int64_t least = (units + max_units - 1) / max_units;
-    int64_t blocks = other * units < want_blocks - 1 + other ? other * units : want_blocks - 1 + other;
-    if (blocks < other * least) blocks = other * least;
-    return blocks;
-}
-
-// step-dependent scalars of the Adam update (bias corrections folded in): step_size = lr / (1 - b1^t), inv_bc2 = 1 / sqrt(1 - b2^t)
-inline void adam_scalars(float lr, int step, float* step_size, float* inv_bc2) {
-    const double bc1 = 1.0 - pow(0.9, (double)step);
-    const double bc2 = 1.0 - pow(0.95, (double)step);
-    *step_size = (float)((double)lr / bc1);
-    *inv_bc2 = (float)(1.0 / sqrt(bc2));
-}
-
-// The test hooks (nadm_hooks.cpp): 0 = the library's own rule.  In libnadm.so they always return 0; in libnadm_testhooks.so they return
-// what nadm_test_force_slices / nadm_test_force_p3_slices / nadm_test_force_generic_mlp last set.
-int hook_p2_slices();
-int hook_p3_slices();
-int hook_generic_mlp();
-
-// the partial sums only (the first kernel of nadm_mlp_bwd_weights): used by the variants of pass 3 that cannot host them
-int mlp_bwd_weight_parts(const nadm_heads_t* hd, int32_t b, const float* Zn, const float* H, const float* dL, const float* dHpre,
-                         const float* dgp, float* small_part, void* stream);
-
-// The genotype passes as the plan's step runs them, with its matmul precision (NADM_PRECISION_*, nadm_plan_set_precision):
-// "highest" calls exactly the public entry point of that form (nadm_decode_bce_sliced / _images / _step, nadm_encode_fwd / _part /
-// _small); "medium" runs the same checks and launches the kernels' medium instantiations (nadm_genotype_passes.hip).
-int decode_bce_prec(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, float* P, int32_t kp, const float* Q, int32_t SP,
-                    float* dP, float* dqpart, float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, const void* qimg,
-                    int32_t n_slices, float* slab, int32_t* counters, int32_t precision, void* stream);
-// small_part == NULL: no side work (then total_chunks > 0 is the launch of one part of a pass, nadm_encode_fwd_part)
-int encode_fwd_prec(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* V, int32_t CP, float* zpart,
-                    int64_t total_chunks, const float* small_part, int32_t splits, int32_t n_small, float* grad_small, float* small,
-                    const nadm_adam_t* adam, int32_t precision, void* stream);
 
 }  // namespace nadm

@@ -345,7 +345,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_a_kernel(nadm_heads_t hd, const f
 // a phase is issued before the first use, and sums over the hidden dimension are thread-partials ->
 // DPP wave sums -> 4-wave combine.
 // =================================================================================================
-constexpr int MLP_JMAX = 8;     // hidden units per thread: JH = 4 (Hd <= 1024) or 8 (Hd <= 2048)
+// (MLP_JMAX = 8 hidden units per thread at most: JH = 4 (Hd <= 1024) or 8 (Hd <= 2048); nadm_pass_args.h)
 constexpr int MLP_KT = 8;       // head columns per pass of the hidden-dimension reductions
 
 template <int SB, int JH, bool C8>
@@ -1293,43 +1293,30 @@ extern "C" int nadm_unpack2bit(const uint8_t* in_dev, uint8_t* out_dev, int64_t 
     return check_launch("unpack2bit");
 }
 
-static int mlp_fwd_impl(const nadm_heads_t* hd, const float* small, const float* zpart, int64_t n_chunks, int32_t b,
-                        float* Z, float* rinv, float* Zn, float* H, float* Q, uint4* qimg, int64_t qimg_head_u4, void* stream) {
-    if (!hd || !small || !zpart || !Z || !rinv || !Zn || !H || !Q) return fail("nadm_mlp_fwd: null pointer");
-    if (b <= 0) return fail("nadm_mlp_fwd: empty batch");
-    if (hd->Hd <= 256 * MLP_JMAX && hd->C <= 8 && !hook_generic_mlp()) {
-        const dim3 grid((b + MLP_SB - 1) / MLP_SB);
+// the MLP forward as the host unit decided it (nadm_passes_host.cpp: mlp_fwd)
+int nadm::launch_mlp_fwd(const MlpFwdLaunch& a) {
+    const nadm_heads_t* hd = a.hd;
+    hipStream_t st = (hipStream_t)a.stream;
+    uint4* const qimg = static_cast<uint4*>(a.qimg);
+    const int64_t qimg_head_u4 = a.qimg_head_bytes / 16;
+    if (a.form == MLP_FAST) {
+        const dim3 grid((a.b + MLP_SB - 1) / MLP_SB);
         const size_t lds = (size_t)(MLP_SB + 1) * hd->SP * 4;                    // s_logit + the head biases
-        const bool c8 = hd->C == 8 && ((reinterpret_cast<uintptr_t>(small) + 4 * (size_t)hd->w1_off) & 15) == 0;
-#define NADM_FWD_LAUNCH(JH, C8) hipLaunchKernelGGL((mlp_fwd_fast_kernel<MLP_SB, JH, C8>), grid, dim3(256), lds, (hipStream_t)stream, *hd, small, zpart, n_chunks, b, Z, rinv, Zn, H, Q, qimg, qimg_head_u4)
-        if (hd->Hd <= 1024) { if (c8) NADM_FWD_LAUNCH(4, true); else NADM_FWD_LAUNCH(4, false); }
-        else { if (c8) NADM_FWD_LAUNCH(8, true); else NADM_FWD_LAUNCH(8, false); }
-#undef NADM_FWD_LAUNCH
-    } else if (hd->Hd <= 2048) {
+        dispatch_bool([&](auto j8, auto c8) {
+            hipLaunchKernelGGL((mlp_fwd_fast_kernel<MLP_SB, decltype(j8)::value ? 8 : 4, decltype(c8)::value>), grid, dim3(256), lds, st, *hd, a.small,
+                               a.zpart, a.n_chunks, a.b, a.Z, a.rinv, a.Zn, a.H, a.Q, qimg, qimg_head_u4);
+        }, a.jh == 8, a.c8);
+    } else if (a.form == MLP_GENERIC4) {
         const size_t lds = (size_t)(1024 + MLP_SB * (hd->CP + hd->Hd + hd->SP)) * 4;
-        hipLaunchKernelGGL((mlp_fwd_kernel<MLP_SB>), dim3((b + MLP_SB - 1) / MLP_SB), dim3(256), lds, (hipStream_t)stream, *hd, small, zpart, n_chunks, b, Z, rinv, Zn, H, Q, qimg, qimg_head_u4);
+        hipLaunchKernelGGL((mlp_fwd_kernel<MLP_SB>), dim3((a.b + MLP_SB - 1) / MLP_SB), dim3(256), lds, st, *hd, a.small, a.zpart, a.n_chunks, a.b, a.Z,
+                           a.rinv, a.Zn, a.H, a.Q, qimg, qimg_head_u4);
     } else {
         const size_t lds = (size_t)(1024 + hd->CP + hd->Hd + hd->SP) * 4;
-        hipLaunchKernelGGL((mlp_fwd_kernel<1>), dim3(b), dim3(256), lds, (hipStream_t)stream, *hd, small, zpart, n_chunks, b, Z, rinv, Zn, H, Q, qimg, qimg_head_u4);
+        hipLaunchKernelGGL((mlp_fwd_kernel<1>), dim3(a.b), dim3(256), lds, st, *hd, a.small, a.zpart, a.n_chunks, a.b, a.Z, a.rinv, a.Zn, a.H, a.Q, qimg,
+                           qimg_head_u4);
     }
     return check_launch("mlp_fwd");
 }
-
-extern "C" int nadm_mlp_fwd(const nadm_heads_t* hd, const float* small, const float* zpart, int64_t n_chunks, int32_t b,
-                            float* Z, float* rinv, float* Zn, float* H, float* Q, void* stream) {
-    return mlp_fwd_impl(hd, small, zpart, n_chunks, b, Z, rinv, Zn, H, Q, nullptr, 0, stream);
-}
-
-extern "C" int nadm_mlp_fwd_images(const nadm_heads_t* hd, const float* small, const float* zpart, int64_t n_chunks, int32_t b,
-                                   float* Z, float* rinv, float* Zn, float* H, float* Q, void* qimg, int64_t qimg_head_bytes, void* stream) {
-    if (!qimg) return fail("nadm_mlp_fwd_images: qimg is NULL (use nadm_mlp_fwd)");
-    if (((uintptr_t)qimg & 15) || (qimg_head_bytes & 15)) return fail("nadm_mlp_fwd_images: qimg and the head stride must be multiples of 16 bytes");
-    if (qimg_head_bytes < nadm_q_image_bytes(b)) return fail("nadm_mlp_fwd_images: head stride smaller than nadm_q_image_bytes(b)");
-    return mlp_fwd_impl(hd, small, zpart, n_chunks, b, Z, rinv, Zn, H, Q, static_cast<uint4*>(qimg), qimg_head_bytes / 16, stream);
-}
-
-extern "C" int nadm_mlp_bwd_weights(const nadm_heads_t* hd, int32_t b, const float* Zn, const float* H, const float* dL,
-                                    const float* dHpre, const float* dgp, float* small_part, float* grad_small, void* stream);
 
 // First level of the dQ reduction for TALL slabs.  Pass 2 leaves one slab row [b, kp] per SNP chunk (1954 rows = 50 MB at
 // M = 500k, K = 8); the MLP backward runs one block per 4 samples and each of its blocks walks all those rows 128 bytes at a
@@ -1397,20 +1384,14 @@ extern "C" int nadm_sum_rows(const float* src, int64_t rows, int64_t n, float* o
     return check_launch("sum_rows");
 }
 
-static int mlp_bwd_impl(const nadm_heads_t* hd, const float* small, float* dqpart, int64_t M, int32_t b,
-                        const float* Z, const float* rinv, const float* Zn, const float* H, const float* Q,
-                        float* dL, float* dHpre, float* dgp, float* small_part, float* dZ, float* grad_small,
-                        const float* losspart, int64_t n_loss, double* loss_acc, void* dzimg, int32_t* dz_counters, void* stream) {
-    if (!hd || !small || !dqpart || !Z || !rinv || !Zn || !H || !Q || !dL || !dHpre || !dgp || !small_part || !dZ)
-        return fail("nadm_mlp_bwd: null pointer");
-    if (dzimg && (!dz_counters || hd->CP > 8 || ((uintptr_t)dzimg & 15)))
-        return fail("nadm_mlp_bwd_image: the image needs its group counters, C <= 8 and 16-byte alignment");
-    bool image_done = false;
-    if (n_loss > 0 && (!losspart || !loss_acc)) return fail("nadm_mlp_bwd: n_loss > 0 needs losspart and loss_acc");
-    if (b <= 0) return fail("nadm_mlp_bwd: empty batch");
-    hipStream_t st = (hipStream_t)stream;
+// the MLP backward as the host unit decided it (nadm_passes_host.cpp: mlp_bwd), behind the dQ pre-reduce of tall slabs; then what the
+// generic kernels and the caller leave to launches of their own: the dZ image, the weight gradients
+int nadm::launch_mlp_bwd(const MlpBwdLaunch& a) {
+    const nadm_heads_t* hd = a.hd;
+    const int32_t b = a.b;
+    hipStream_t st = (hipStream_t)a.stream;
     DqChunks dqc;
-    for (int h = 0; h < NADM_MAX_HEADS; ++h) dqc.n[h] = dqc.full[h] = h < hd->n_heads ? nadm_decode_chunks(M, hd->kp[h]) : 0;
+    for (int h = 0; h < NADM_MAX_HEADS; ++h) dqc.n[h] = dqc.full[h] = h < hd->n_heads ? nadm_decode_chunks(a.M, hd->kp[h]) : 0;
     {   // tall slabs are folded to DQ_R rows first (dqpart is scratch of the step: reduced in place)
         int64_t max_rows = 0, max_row4 = 0;
         for (int h = 0; h < hd->n_heads; ++h) {
@@ -1419,52 +1400,33 @@ static int mlp_bwd_impl(const nadm_heads_t* hd, const float* small, float* dqpar
         }
         if (max_rows > DQ_R_MIN_ROWS) {
             hipLaunchKernelGGL(dq_prereduce_kernel, dim3((unsigned)((max_row4 + 255) / 256), DQ_R, hd->n_heads), dim3(256), 0, st,
-                               dqpart, dqc, *hd, b);
+                               a.dqpart, dqc, *hd, b);
             if (check_launch("dq_prereduce")) return 1;
             for (int h = 0; h < hd->n_heads; ++h)                       // the kernel's rule: heads with more than DQ_R rows were folded
                 if (dqc.n[h] > DQ_R) dqc.n[h] = DQ_R;
         }
     }
-    if (hd->Hd <= 256 * MLP_JMAX && hd->C <= 8 && !hook_generic_mlp()) {
-        const dim3 grid((b + MLP_SB - 1) / MLP_SB + (n_loss > 0 ? 1 : 0));          // + the loss block
+    if (a.form == MLP_FAST) {
+        const dim3 grid((b + MLP_SB - 1) / MLP_SB + (a.n_loss > 0 ? 1 : 0));          // + the loss block
         const size_t lds = (size_t)3 * MLP_SB * hd->SP * 4;                      // s_dl + the block's Q rows + dL
-        const bool c8 = hd->C == 8 && ((reinterpret_cast<uintptr_t>(small) + 4 * (size_t)hd->w1_off) & 15) == 0;
-#define NADM_BWD_LAUNCH(JH, C8) hipLaunchKernelGGL((mlp_bwd_a_fast_kernel<MLP_SB, JH, C8>), grid, dim3(256), lds, st, *hd, small, dqpart, dqc, b, Z, rinv, H, Q, \
-                                                   dL, dHpre, dgp, dZ, losspart, n_loss, loss_acc, (uint4*)dzimg, dz_counters)
-        image_done = dzimg != nullptr;
-        if (hd->Hd <= 1024) { if (c8) NADM_BWD_LAUNCH(4, true); else NADM_BWD_LAUNCH(4, false); }
-        else { if (c8) NADM_BWD_LAUNCH(8, true); else NADM_BWD_LAUNCH(8, false); }
-#undef NADM_BWD_LAUNCH
-    } else if (hd->Hd <= 2048) {
+        dispatch_bool([&](auto j8, auto c8) {
+            hipLaunchKernelGGL((mlp_bwd_a_fast_kernel<MLP_SB, decltype(j8)::value ? 8 : 4, decltype(c8)::value>), grid, dim3(256), lds, st, *hd, a.small,
+                               a.dqpart, dqc, b, a.Z, a.rinv, a.H, a.Q, a.dL, a.dHpre, a.dgp, a.dZ, a.losspart, a.n_loss, a.loss_acc, (uint4*)a.dzimg,
+                               a.dz_counters);
+        }, a.jh == 8, a.c8);
+    } else if (a.form == MLP_GENERIC4) {
         const size_t lds = (size_t)(1024 + MLP_SB * (hd->SP + hd->CP + hd->Hd)) * 4;
-        hipLaunchKernelGGL((mlp_bwd_a_kernel<MLP_SB>), dim3((b + MLP_SB - 1) / MLP_SB), dim3(256), lds, st, *hd, small, dqpart, dqc, b, Z, rinv, H, Q,
-                           dL, dHpre, dgp, dZ, losspart, n_loss, loss_acc);
+        hipLaunchKernelGGL((mlp_bwd_a_kernel<MLP_SB>), dim3((b + MLP_SB - 1) / MLP_SB), dim3(256), lds, st, *hd, a.small, a.dqpart, dqc, b, a.Z, a.rinv,
+                           a.H, a.Q, a.dL, a.dHpre, a.dgp, a.dZ, a.losspart, a.n_loss, a.loss_acc);
     } else {
         const size_t lds = (size_t)(1024 + hd->SP + hd->CP + hd->Hd) * 4;
-        hipLaunchKernelGGL((mlp_bwd_a_kernel<1>), dim3(b), dim3(256), lds, st, *hd, small, dqpart, dqc, b, Z, rinv, H, Q,
-                           dL, dHpre, dgp, dZ, losspart, n_loss, loss_acc);
+        hipLaunchKernelGGL((mlp_bwd_a_kernel<1>), dim3(b), dim3(256), lds, st, *hd, a.small, a.dqpart, dqc, b, a.Z, a.rinv, a.H, a.Q,
+                           a.dL, a.dHpre, a.dgp, a.dZ, a.losspart, a.n_loss, a.loss_acc);
     }
     if (check_launch("mlp_bwd")) return 1;
-    if (dzimg && !image_done && nadm_dz_image(dZ, b, hd->CP, dzimg, stream)) return 1;     // the generic kernels: the image as a launch of its own
-    if (!grad_small) return 0;                       // the caller runs nadm_mlp_bwd_weights itself (possibly on another stream)
-    return nadm_mlp_bwd_weights(hd, b, Zn, H, dL, dHpre, dgp, small_part, grad_small, stream);
-}
-
-extern "C" int nadm_mlp_bwd(const nadm_heads_t* hd, const float* small, float* dqpart, int64_t M, int32_t b,
-                            const float* Z, const float* rinv, const float* Zn, const float* H, const float* Q,
-                            float* dL, float* dHpre, float* dgp, float* small_part, float* dZ, float* grad_small,
-                            const float* losspart, int64_t n_loss, double* loss_acc, void* stream) {
-    return mlp_bwd_impl(hd, small, dqpart, M, b, Z, rinv, Zn, H, Q, dL, dHpre, dgp, small_part, dZ, grad_small, losspart, n_loss, loss_acc,
-                        nullptr, nullptr, stream);
-}
-
-extern "C" int nadm_mlp_bwd_image(const nadm_heads_t* hd, const float* small, float* dqpart, int64_t M, int32_t b,
-                                  const float* Z, const float* rinv, const float* Zn, const float* H, const float* Q,
-                                  float* dL, float* dHpre, float* dgp, float* small_part, float* dZ, float* grad_small,
-                                  const float* losspart, int64_t n_loss, double* loss_acc, void* dzimg, int32_t* dz_counters, void* stream) {
-    if (!dzimg || !dz_counters) return fail("nadm_mlp_bwd_image: null pointer");
-    return mlp_bwd_impl(hd, small, dqpart, M, b, Z, rinv, Zn, H, Q, dL, dHpre, dgp, small_part, dZ, grad_small, losspart, n_loss, loss_acc,
-                        dzimg, dz_counters, stream);
+    if (a.dzimg && a.form != MLP_FAST && nadm_dz_image(a.dZ, b, hd->CP, a.dzimg, a.stream)) return 1;     // the generic kernels: the image as a launch of its own
+    if (!a.grad_small) return 0;                     // the caller runs nadm_mlp_bwd_weights itself (possibly on another stream)
+    return nadm_mlp_bwd_weights(hd, b, a.Zn, a.H, a.dL, a.dHpre, a.dgp, a.small_part, a.grad_small, a.stream);
 }
 
 extern "C" int nadm_mlp_bwd_weights(const nadm_heads_t* hd, int32_t b, const float* Zn, const float* H, const float* dL,

@@ -310,13 +310,18 @@ int flush_small(nadm_plan* p, void* stream) {
     return 0;
 }
 
+// pass 1 over the whole matrix in the plan's matmul precision, no side blocks
+Pass1Launch pass1_of(const nadm_plan* p, const int32_t* idx, int b, void* stream) {
+    const nadm_plan_desc_t& d = p->d;
+    return Pass1Launch{d.xp, d.ld, idx, b, d.M, d.params + p->lay.off_v, d.heads.CP, d.zpart, 0, 0u, p->precision == NADM_PRECISION_MEDIUM, SmallSide{}, stream};
+}
+
 // DP mode: pass 1 in the parts message B's buckets cut V into.  Part j reads V's range j only, so it waits for bucket j of the
 // previous step only (part 0, on the compute stream, also makes the small parameters final for the MLP forward behind it); the
 // parts 1.. run on streams of their own beside it and join the compute stream.  One bucket: one launch, one wait.
 int encode_fwd_parts(nadm_plan* p, const int32_t* idx, int b, hipStream_t st) {
     const nadm_plan_desc_t& d = p->d;
     const nadm_heads_t& hd = d.heads;
-    const float* V = d.params + p->lay.off_v;
     if (p->nb > 1) HIP_OK(hipEventRecord(p->ev_fork1, st), "hipEventRecord");     // the parts may not overtake what the compute stream still holds (zpart's readers, idx)
     for (int j = 0; j < p->nb; ++j) {
         hipStream_t fs = j == 0 ? st : p->fan[j];
@@ -324,10 +329,11 @@ int encode_fwd_parts(nadm_plan* p, const int32_t* idx, int b, hipStream_t st) {
         if (p->b_pending) HIP_OK(hipStreamWaitEvent(fs, p->ev_g[j], 0), "hipStreamWaitEvent");
         const int64_t m0 = p->lay.bkt_m0[j], m1 = p->lay.bkt_m0[j + 1];
         if (p->nb == 1) {
-            if (encode_fwd_prec(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, p->precision, fs)) return 1;
-        } else if (encode_fwd_prec(d.xp + m0 / 4, d.ld, idx, b, m1 - m0, V + m0 * hd.CP, hd.CP, d.zpart + nadm_encode_chunks(m0) * (int64_t)b * hd.CP,
-                                   p->enc_chunks, nullptr, 0, 0, nullptr, nullptr, nullptr, p->precision, fs)) {
-            return 1;
+            if (pass1(pass1_of(p, idx, b, fs))) return 1;
+        } else {
+            Pass1Launch a = pass1_of(p, idx, b, fs);                 // one part of the pass: the SNP range of bucket j
+            a.xp += m0 / 4; a.M = m1 - m0; a.V += m0 * hd.CP; a.zpart += nadm_encode_chunks(m0) * (int64_t)b * hd.CP; a.total_chunks = p->enc_chunks;
+            if (pass1(a)) return 1;
         }
         if (j > 0) HIP_OK(hipEventRecord(p->ev_p1[j], fs), "hipEventRecord");
     }
@@ -340,20 +346,18 @@ int encode_fwd_parts(nadm_plan* p, const int32_t* idx, int b, hipStream_t st) {
 int forward(nadm_plan* p, const int32_t* idx, int b, void* stream) {
     const nadm_plan_desc_t& d = p->d;
     const nadm_heads_t& hd = d.heads;
-    float* V = d.params + p->lay.off_v;
     Timed t1{p, NADM_T_ENCODE_FWD, (hipStream_t)stream};
     if (t1.begin()) return 1;
     if (d.mode == NADM_MODE_DP) {
         if (encode_fwd_parts(p, idx, b, (hipStream_t)stream)) return 1;
     } else if (p->small_pending && hd.CP <= 8) {
         const nadm_adam_t sa = adam_at(p, 0, p->pend_lr, p->pend_step, p->pend_scale);
-        if (encode_fwd_prec(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, 0, d.small_part, p->pend_splits, hd.n_small, d.grads, d.params, &sa,
-                            p->precision, stream))
-            return 1;
+        Pass1Launch a = pass1_of(p, idx, b, stream);
+        if (pass1_small_args(a, d.small_part, p->pend_splits, hd.n_small, d.grads, d.params, &sa) || pass1(a)) return 1;
         p->small_pending = false;
     } else {
         if (flush_small(p, stream)) return 1;
-        if (encode_fwd_prec(d.xp, d.ld, idx, b, d.M, V, hd.CP, d.zpart, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, p->precision, stream)) return 1;
+        if (pass1(pass1_of(p, idx, b, stream))) return 1;
     }
     if (t1.end()) return 1;
     const float* zsrc = d.zpart;
@@ -365,9 +369,8 @@ int forward(nadm_plan* p, const int32_t* idx, int b, void* stream) {
     }
     Timed t2{p, NADM_T_MLP_FWD, (hipStream_t)stream};
     if (t2.begin()) return 1;
-    const int rc = d.qimg ? nadm_mlp_fwd_images(&hd, d.params, zsrc, zrows, b, d.Z, d.rinv, d.Zn, d.H, d.Q, d.qimg, d.qimg_head_bytes, stream)
-                          : nadm_mlp_fwd(&hd, d.params, zsrc, zrows, b, d.Z, d.rinv, d.Zn, d.H, d.Q, stream);
-    if (rc) return 1;
+    if (mlp_fwd(MlpFwdLaunch{&hd, d.params, zsrc, zrows, b, d.Z, d.rinv, d.Zn, d.H, d.Q, d.qimg != nullptr, d.qimg, d.qimg ? d.qimg_head_bytes : 0, stream}))
+        return 1;
     return t2.end();
 }
 
@@ -399,10 +402,13 @@ int decode_heads(nadm_plan* p, const int32_t* idx, int b, int with_loss, const f
         const int slices = d.p2_slab ? nadm_decode_slices(b, d.M, kp) : 1;     // sample slices where the SNP chunks alone leave CUs idle
         if (slices > 1 && slices > p->slices_cap[h])                           // (the rule is a function of (b, M, kp); only the test build can move it)
             return fail("nadm_step: pass 2 would be cut into more sample slices than the plan's slab was sized for at creation");
-        // (sliced / from the Q images / splitting Q itself: nadm_decode_bce_sliced / _images / _step, in the plan's precision)
-        if (decode_bce_prec(d.xp, d.ld, idx, b, d.M, Ph, kp, Qh, hd.SP, dPh, slab, lossp, flags, xg, adp, qi, slices,
-                            slices > 1 ? d.p2_slab + p->slab_off[h] : nullptr, slices > 1 ? d.p2_cnt + p->loss_off[h] : nullptr, p->precision, st))
-            return 1;
+        // sliced / from the Q images / splitting Q itself, in the plan's precision; "highest" is refused in the words of the public form
+        // of the same shape (nadm_decode_bce_sliced / _images / _step), "medium" in the step's own
+        const bool medium = p->precision == NADM_PRECISION_MEDIUM;
+        Pass2Launch a{d.xp, d.ld, idx, b, d.M, Ph, kp, Qh, hd.SP, dPh, slab, lossp, flags, xg, qi, slices,
+                      slices > 1 ? d.p2_slab + p->slab_off[h] : nullptr, slices > 1 ? d.p2_cnt + p->loss_off[h] : nullptr, medium, st};
+        const char* who = medium ? "nadm_step" : slices > 1 ? "nadm_decode_bce_sliced" : qi ? "nadm_decode_bce_images" : "nadm_decode_bce_step";
+        if (pass2_step_args(a, who, adp, !medium && slices <= 1 && !qi) || pass2(a)) return 1;
         dq_off += p->dec_chunks[h] * (int64_t)b * kp;
     }
     if (fan > 1) {
@@ -652,11 +658,9 @@ static int step_impl(nadm_plan_t* p, const int32_t* idx, int32_t b, float lr, in
     if (t3.begin()) return 1;
     const int64_t nl = with_loss ? n_loss : 0;
     const bool image = hd.CP <= 8;
-    const int rc = image ? nadm_mlp_bwd_image(&hd, d.params, dq_src, dq_M, b, d.Z, d.rinv, d.Zn, d.H, d.Q, d.dL, d.dHpre, d.dgp, d.small_part, d.dZ,
-                                              nullptr, d.losspart, nl, d.loss_acc, d.dzimg, d.dzcnt, stream)
-                         : nadm_mlp_bwd(&hd, d.params, dq_src, dq_M, b, d.Z, d.rinv, d.Zn, d.H, d.Q, d.dL, d.dHpre, d.dgp, d.small_part, d.dZ,
-                                        nullptr, d.losspart, nl, d.loss_acc, stream);
-    if (rc) return 1;
+    if (mlp_bwd(MlpBwdLaunch{&hd, d.params, dq_src, dq_M, b, d.Z, d.rinv, d.Zn, d.H, d.Q, d.dL, d.dHpre, d.dgp, d.small_part, d.dZ, nullptr, d.losspart, nl,
+                             d.loss_acc, image, image ? d.dzimg : nullptr, image ? d.dzcnt : nullptr, stream}))
+        return 1;
     if (t3.end()) return 1;
 
     // ---- pass 3: dV = X^T.dZ from the batch copy pass 2 left (C <= 8) + the MLP weight-gradient partials as side blocks
@@ -684,9 +688,9 @@ static int step_impl(nadm_plan_t* p, const int32_t* idx, int32_t b, float lr, in
             if (parts || j == 0) {
                 const int64_t m0 = parts ? p->lay.bkt_m0[j] : 0, m1 = parts ? p->lay.bkt_m0[j + 1] : d.M;
                 const uint8_t* xsrc = image ? d.xg + (m0 / 4) * (int64_t)b : d.xp + m0 / 4;
-                if (nadm_encode_bwd_step(xsrc, d.ld, idx, b, m1 - m0, d.dZ, image ? d.dzimg : nullptr, hd.CP, V + m0 * hd.CP, dV + m0 * hd.CP, nullptr,
-                                         j == 0 ? &mw : nullptr, p3_flags, stream))
-                    return 1;
+                Pass3Launch a{xsrc, d.ld, idx, b, m1 - m0, d.dZ, image ? d.dzimg : nullptr, hd.CP, V + m0 * hd.CP, dV + m0 * hd.CP, j == 0 ? &mw : nullptr,
+                              p3_flags, 0u, 1, nullptr, nullptr, stream};
+                if (pass3_step_args(a, "nadm_encode_bwd_step", nullptr, false) || pass3(a)) return 1;
                 if (!parts || j == p->nb - 1) { if (t4.end()) return 1; }
                 if (p->nb > 1)
                     for (int i = j; i < (parts ? j + 1 : p->nb); ++i) HIP_OK(hipEventRecord(p->ev_b[i], st), "hipEventRecord");
@@ -715,9 +719,10 @@ static int step_impl(nadm_plan_t* p, const int32_t* idx, int32_t b, float lr, in
     const nadm_adam_t av = adam_at(p, p->lay.off_v, lr, p->step_count, scale);
     const int p3_slices = (d.p3_slab && image) ? nadm_encode_slices(b, d.M, hd.CP) : 1;      // sample slices where the SNP chunks alone leave CUs idle
     if (p3_slices > p->p3_slices_cap) return fail("nadm_step: pass 3 would be cut into more sample slices than the plan's slab was sized for at creation");
-    if (p3_slices > 1) {
-        if (nadm_encode_bwd_sliced(d.xg, d.ld, idx, b, d.M, d.dZ, d.dzimg, hd.CP, V, dV, &av, &mw, p3_flags, p3_slices, d.p3_slab, d.p3_cnt, stream)) return 1;
-    } else if (nadm_encode_bwd_step(image ? d.xg : d.xp, d.ld, idx, b, d.M, d.dZ, image ? d.dzimg : nullptr, hd.CP, V, dV, &av, &mw, p3_flags, stream)) return 1;
+    const bool p3_sliced = p3_slices > 1;                        // (then image holds: the sliced form's operands are the unsliced form's)
+    Pass3Launch a3{image ? d.xg : d.xp, d.ld, idx, b, d.M, d.dZ, image ? d.dzimg : nullptr, hd.CP, V, dV, &mw, p3_flags, 0u, p3_slices,
+                   p3_sliced ? d.p3_slab : nullptr, p3_sliced ? d.p3_cnt : nullptr, stream};
+    if (pass3_step_args(a3, p3_sliced ? "nadm_encode_bwd_sliced" : "nadm_encode_bwd_step", &av, p3_sliced) || pass3(a3)) return 1;
     if (t4.end()) return 1;
 
     // ---- the small parameters

@@ -984,3 +984,22 @@ def test_matrix_passes_refuse_rows_of_4_gib():
     ld = 1 << 32
     assert lib.nadm_encode_fwd(fake, ld, fake, 16, 4 * ld, fake, 8, fake, None) != 0 and b"4 GiB" in lib.nadm_last_error()
     assert lib.nadm_decode_bce(fake, ld, fake, 16, 4 * ld, fake, 8, fake, 8, fake, fake, fake, 1, None) != 0 and b"4 GiB" in lib.nadm_last_error()
+
+
+def test_host_selfcheck_builds_and_passes(tmp_path):
+    """csrc/host_selfcheck.cpp as a plain program (no sanitizer, no GPU): the host units on their edge inputs and the host side of the
+    genotype passes and the MLP pair (csrc/nadm_passes_host.cpp) linked against launchers that only record the struct they are given --
+    which form, batch split and slice count every entry point decides, the slice rules at their edges and against a brute-force maximum,
+    the forced slice counts of the test build, and every refusal above before any launcher is reached.  (The AddressSanitizer + UBSan
+    build of the same program is the stand-alone command in tools/README.md.)"""
+    import shutil
+    import subprocess
+    if shutil.which("hipcc") is None:
+        pytest.skip("no hipcc")
+    csrc = os.path.join(ROOT, "neural-admixture_amd", "csrc")
+    exe = str(tmp_path / "host_selfcheck")
+    units = ["host_selfcheck.cpp", "nadm_host_io.cpp", "nadm_layout.cpp", "nadm_passes_host.cpp", "nadm_hooks.cpp"]
+    subprocess.run(["hipcc", "-std=c++17", "-O1", "-Wall", "-DNADM_TEST_HOOKS", "-o", exe] + [os.path.join(csrc, u) for u in units] + ["-lpthread"],
+                   check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip().endswith("host_selfcheck ok"), (run.stdout, run.stderr)
