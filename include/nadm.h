@@ -638,6 +638,38 @@ int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba,
                  const float* P, int32_t k, int32_t kp, const float* QA, const float* QB, int32_t q_stride, float pimin,
                  double* num, double* den, int32_t* nobs, float* scratch, void* stream);
 
+/* ---- KING-robust kinship (Manichaikul et al. 2010) of one block of sample pairs, from the genotypes alone -----------------------
+ * The check of the "unrelated samples" assumption BEFORE a fit: it needs no allele frequencies and no model, and it is robust to
+ * population structure.  One call = the rows idxA[0..ba) against the rows idxB[0..bb) (idx == NULL: rows 0..b; any order, a
+ * duplicate row is allowed, the two lists may be the same).  Codes 0, 1, 2 are observed, 3 is missing.  For samples a, b, over the
+ * SNPs j < M at which BOTH are observed:
+ *     n      = the number of such SNPs
+ *     hethet = #(g_a = 1 and g_b = 1)
+ *     ibs0   = #(g_a = 0, g_b = 2) + #(g_a = 2, g_b = 0)
+ *     het_a  = #(g_a = 1),   het_b = #(g_b = 1)                     (each among the jointly observed SNPs)
+ *     phi_ab = 1/2 - (het_a + het_b - 2 hethet + 4 ibs0) / (4 min(het_a, het_b))
+ * phi_ab is NaN where min(het_a, het_b) = 0.  The library returns the five counts; the caller forms the numerator as an integer and
+ * divides once, in float64.  Expected: 0.5 for a duplicate (exactly 0.5 on the diagonal whenever the sample has a heterozygous
+ * call), 0.25 for first degree, 0.125 for second degree, 0 for an unrelated pair from one population, NEGATIVE for unrelated pairs
+ * from different populations (the estimator's known behaviour, harmless for a cutoff).  The statistic does not change under the
+ * reader's 0 <-> 2 flip.  This is the between-family "robust" estimator with the min denominator; neither KING's nor plink2's
+ * printed digits are promised, only this formula.
+ * counts int32 [5, ba, bb], row-major: n, hethet, ibs0, het_a, het_b.  ba, bb in 1..NADM_KING_MAX_ROWS, 0 < M < 2^31 (the counts are
+ * int32).  scratch: nadm_king_scratch_ints(ba, bb, M) int32 (grows with ba, bb and M; <= 0: the shape is refused).  xp and scratch
+ * 16-byte, idxA, idxB and counts 4-byte aligned; ld >= ceil(M/4), ld % 16 == 0, ld < 2^32.
+ * The sums run on the matrix pipe (v_mfma_i32_16x16x64_i8, the SNP axis on its k): per side a call enters as the four 0 / 1 int8
+ * indicators h (code 1), z0 (code 0), z2 (code 2) and o (observed); six products per tile -- h.h, z0.z2 + z2.z0, h.o, o.h, o.o --
+ * give the five counts, int32 and EXACT.  SNPs >= M, the pad fields of a row's last byte, the bytes behind it and rows past the
+ * list enter as the missing code: exactly 0 in every count.  The 256-SNP chunks are cut into nadm_king_ranges(ba, bb, M) contiguous
+ * ranges (more than one while the 64 x 64 tiles of the block alone do not fill the chip); a second launch adds the ranges'
+ * partials in range order.  No floating point and no atomics on the device: the same inputs give the same bits.  Every refusal is
+ * reported before anything is launched.  Asynchronous on `stream`. */
+#define NADM_KING_MAX_ROWS 4096
+int32_t nadm_king_ranges(int32_t ba, int32_t bb, int64_t M);
+int64_t nadm_king_scratch_ints(int32_t ba, int32_t bb, int64_t M);
+int nadm_king(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
+              int32_t* counts, int32_t* scratch, void* stream);
+
 /* ---- LD pruning: windowed r^2 of neighbouring SNPs on the matrix pipe, and the keep-list ---------------------------------------
  * ADMIXTURE-type models assume SNPs in linkage equilibrium; the usual preparation is plink's --indep-pairwise.  These entries do it
  * on the packed matrix already in HBM.  Codes g in {0, 1, 2} are observed, 3 is missing; o = 1 where a call is observed, else 0.

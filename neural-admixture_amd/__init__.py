@@ -12,6 +12,7 @@ from .train import train          # noqa: F401
 from .project import project_q    # noqa: F401  (Q refined against a fixed P, no encoder needed)
 from .project import project_p, polish    # noqa: F401  (P refitted against a fixed Q; the two alternated)
 from .relate import kinship, kinship_pairs    # noqa: F401  (admixture-aware kinship of sample pairs from Q and P)
+from .king import king_pairs, unrelated_set, select_samples    # noqa: F401  (KING-robust kinship from the genotypes alone, the unrelated set, the selection of samples; the dense form is king.king)
 from .ld import snp_counts, ld_band, prune, select_snps    # noqa: F401  (LD pruning: windowed r^2, the keep-list, the selection)
 from .hwe import snp_hwe, snp_hwe_sums, hwe_keep    # noqa: F401  (Hardy-Weinberg score test given ancestry, per SNP, from Q and P)
 from .cv import cv_error, mask_fold, heldout_deviance    # noqa: F401  (cross-validation error for choosing K, over held-out calls)
@@ -22,7 +23,7 @@ from . import pca                 # noqa: F401  (principal components of the sta
 from .pca import obs_project, obs_project_t    # noqa: F401  (its two products: the observed-calls pair products)
 from . import pack2bit            # noqa: F401  (the reference's native module by its own names: pack2bit.cu:144-147)
 
-__all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish", "kinship", "kinship_pairs",
+__all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish", "kinship", "kinship_pairs", "king_pairs", "unrelated_set", "select_samples",
            "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep", "cv_error", "mask_fold", "heldout_deviance",
            "bootstrap_q", "block_weights", "p_se", "p_info", "se_from_info", "resid_cor", "em_sums", "fit_check", "group_means",
            "sample_means", "pca", "obs_project", "obs_project_t"]

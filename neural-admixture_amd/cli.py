@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|kinship|prune|hwe|cv|bootstrap|pse|fit|pca ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|king|kinship|prune|hwe|cv|bootstrap|pse|fit|pca ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -20,7 +20,8 @@ import torch
 
 from .engine import row_ranges
 from .train import AFTER_KEYWORDS, AFTER_TRAINING
-from .io import chrom_codes, find_run_files, read_bim, read_id_list, read_run_matrix, resolve_ids, write_id_list
+from .io import (chrom_codes, find_run_files, read_bim, read_fam, read_id_list, read_run_matrix, read_sample_list, resolve_ids,
+                 resolve_samples, write_id_list)
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(message)s")
 log = logging.getLogger(__name__)
@@ -36,6 +37,15 @@ def _add_extract(p):
     p.add_argument("--extract", type=str, default=None, metavar="FILE",
                    help="use only the SNPs whose IDs (column 2 of the .bim) FILE lists, one per line -- a {name}.prune.in of the 'prune' "
                         "mode, or any list plink --extract would read.  BED input only.  Default: every SNP")
+
+
+def _add_samples(p):
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--keep", type=str, default=None, metavar="FILE",
+                   help="use only the samples FILE lists, one 'FID IID' (or the IID alone) per line as in the .fam -- a {name}.king.in of "
+                        "the 'king' mode, or any list plink --keep would read.  BED input only.  Default: every sample")
+    g.add_argument("--remove", type=str, default=None, metavar="FILE",
+                   help="leave out the samples FILE lists (a {name}.king.out, or any list plink --remove would read).  BED input only")
 
 
 def parse_train_args(argv):
@@ -102,6 +112,7 @@ def parse_train_args(argv):
                         "at most 4096 samples are taken (a seeded subset above that).  Single-GPU, unsupervised runs only")
     _add_precision(p)
     _add_extract(p)
+    _add_samples(p)
     return p.parse_args(argv)
 
 
@@ -123,13 +134,14 @@ def parse_infer_args(argv):
                    help="stop refining a batch once no entry of Q moves by this much in a step")
     _add_precision(p)
     _add_extract(p)
+    _add_samples(p)
     return p.parse_args(argv)
 
 
 def _add_run_args(p, multi_k, out="files"):
     """What the analysis parsers share: where the data and the run's files are, the K of the run (``multi_k``: --k or --min_k ..
-    --max_k; False: one required --k; None: no K), the host threads and -- unless ``out`` is None -- the output name (of the written
-    ``out``) and --extract."""
+    --max_k; False: one required --k; None: no K), the host threads, --keep / --remove and -- unless ``out`` is None -- the output
+    name (of the written ``out``) and --extract."""
     for flag in ("--data_path", "--save_dir", "--name"):
         p.add_argument(flag, required=True, type=str)
     if multi_k is not None:
@@ -138,6 +150,7 @@ def _add_run_args(p, multi_k, out="files"):
         p.add_argument("--min_k", type=int)
         p.add_argument("--max_k", type=int)
     p.add_argument("--threads", type=int, default=1)
+    _add_samples(p)
     if out is not None:
         p.add_argument("--out_name", type=str, default=None, help=f"name of the written {out} (default: --name)")
         _add_extract(p)
@@ -151,6 +164,19 @@ def parse_kinship_args(argv):
                    help="list the pairs with a kinship coefficient of at least this (default 0.0442, the lower edge of third-degree relatives)")
     p.add_argument("--pimin", type=float, default=0.0,
                    help="drop a call whose individual-specific allele frequency is outside [pimin, 1 - pimin] (default 0: every observed call counts)")
+    return p.parse_args(argv)
+
+
+def parse_king_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture king",
+                                description="KING-robust kinship of the samples from the genotype file alone, and a maximal set of "
+                                            "unrelated samples to train on")
+    _add_run_args(p, multi_k=None, out=None)
+    _add_extract(p)
+    p.add_argument("--cutoff", type=float, default=2.0 ** -3.5,
+                   help="a pair with a kinship coefficient of at least this is related (default 0.0884, the lower edge of second-degree "
+                        "relatives): it is listed, and one of its samples goes to the .king.out list")
+    p.add_argument("--rows", type=int, default=1024, help="samples per side of a block of pairs, 1..4096 (default 1024)")
     return p.parse_args(argv)
 
 
@@ -372,11 +398,47 @@ def _extract_keep(data_path, extract):
     return keep
 
 
-def _read_on_gpu(args, keep=None):
+def _fam_ids(data_path):
+    """The (FID, IID) of every sample of a BED input, before any genotype is read: ``_bed_shape`` and the .fam's first two columns."""
+    from pathlib import Path
+    _bed_shape(data_path, need_bim=False)
+    return read_fam(Path(data_path).with_suffix(".fam"))
+
+
+def _sample_keep(args):
+    """--keep FILE / --remove FILE -> bool [N] over the samples of the .fam, before any genotype is read; None without either flag.
+    VCF input, a missing file, non-unique IDs in the .fam and a name it does not hold end the run, naming the offender."""
+    flag = "--keep" if args.keep else "--remove" if args.remove else None
+    if flag is None:
+        return None
+    path = args.keep or args.remove
+    _need_bed(args.data_path, f"{flag} resolves sample IDs through a .fam file", ".bed or .vcf")
+    if not os.path.isfile(path):
+        raise SystemExit(f"    {path} not found.")
+    fam = _fam_ids(args.data_path)
+    from pathlib import Path
+    named = resolve_samples(fam, read_sample_list(path), str(Path(args.data_path).with_suffix(".fam")), path)
+    keep = named if args.keep else ~named
+    if not keep.any():
+        raise SystemExit(f"    {flag} {path} leaves no sample.")
+    return keep
+
+
+def _filter_lines(lines, samples, path):
+    """The lines of a one-line-per-sample-of-the-.fam file (``--pops_path``) that belong to the samples --keep / --remove leave."""
+    if samples is None:
+        return lines
+    if len(lines) != len(samples):
+        raise SystemExit(f"    {path} holds {len(lines)} lines, the .fam {len(samples)} samples (one line per sample of the .fam, "
+                         "before --keep / --remove).")
+    return [ln for ln, k in zip(lines, samples) if k]
+
+
+def _read_on_gpu(args, keep=None, samples=None):
     """What an analysis mode does once its arguments and files are in order: the GPU check, the host threads, the genotypes in HBM."""
     _need_gpu()
     torch.set_num_threads(max(1, args.threads))
-    return _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
+    return _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep, samples=samples)
 
 
 def _out_stem(args):
@@ -402,7 +464,8 @@ def _prune_main(argv):
         raise SystemExit("    --r2 must be in [0, 1].")
     _need_bed(args.data_path, "prune needs the SNP IDs and chromosomes of a .bim file")
     _, _, _, ids, chroms = _bed_ids(args.data_path)         # before the GPU check and before any genotype is read
-    data = _read_on_gpu(args)
+    samples = _sample_keep(args)
+    data = _read_on_gpu(args, samples=samples)
     keep, stats = ld.prune(data.packed, data.M, args.window, args.r2, chrom=chrom_codes(chroms))
     os.makedirs(args.save_dir, exist_ok=True)
     _write_id_lists(os.path.join(args.save_dir, f"{args.name}.prune"), ids, keep)
@@ -421,6 +484,7 @@ def _pca_main(argv):
     except RuntimeError as e:
         raise SystemExit(f"    {e}") from None
     keep = _extract_keep(args.data_path, args.extract)     # before the GPU check and before any genotype is read
+    samples = _sample_keep(args)
     name = os.path.basename(args.data_path)
     if ".vcf" in name:
         if not os.path.isfile(args.data_path):
@@ -429,7 +493,7 @@ def _pca_main(argv):
         _bed_shape(args.data_path, need_bim=False)
     else:
         raise SystemExit("    Invalid format. Unrecognized file format. Make sure file ends with .bed or .vcf.")
-    data = _read_on_gpu(args, keep)
+    data = _read_on_gpu(args, keep, samples)
     res = pca.pca(data.packed, data.M, pcs=args.pcs, oversample=args.oversample, iters=args.iters, maf=args.maf, seed=args.seed)
     pca.log_result(res, log)
     pca.write_result(_out_stem(args), res)
@@ -500,15 +564,18 @@ def _load_run_heads(args, ks, paths, keep, check_n=None):
     (the .P files then have one row per listed SNP).  ``check_n(N)``: a mode's own check of the sample count, as early as N is known."""
     P_paths, Q_paths = paths
     n_known = m_known = None
+    samples = _sample_keep(args)                           # (the .Q files then have one row per kept sample)
     if ".bed" in os.path.basename(args.data_path):
         n_known, m_known, _ = _bed_shape(args.data_path, need_bim=False)
         if keep is not None:
             m_known = int(keep.sum())
+        if samples is not None:
+            n_known = int(samples.sum())
     Qs = [read_run_matrix(p, k, n_known) for p, k in zip(Q_paths, ks)]
     Ps = [read_run_matrix(p, k, m_known, "model" if m_known is not None else "data") for p, k in zip(P_paths, ks)]
     if check_n is not None and n_known is not None:
         check_n(n_known)
-    data = _read_on_gpu(args, keep)
+    data = _read_on_gpu(args, keep, samples)
     if check_n is not None and n_known is None:
         check_n(data.N)
     for paths_, mats, rows in ((Q_paths, Qs, data.N), (P_paths, Ps, data.M)):
@@ -619,6 +686,41 @@ def _fit_main(argv):
     log.info("    Residual correlations saved.")
 
 
+def _king_main(argv):
+    """``king`` mode: the genotypes alone -> {name}.king (``i j phi n hethet ibs0`` per pair at or above --cutoff, 0-based indices
+    among the samples analysed, by i then j) and {name}.king.in / .king.out, the kept and the removed samples of ``king.unrelated_set`` as ``FID IID``
+    lines of the .fam (readable by plink --keep / --remove and by --keep / --remove here)."""
+    from pathlib import Path
+    from . import king, relate
+    from .io import check_unique_samples, write_sample_list
+    args = parse_king_args(argv)
+    if not args.cutoff == args.cutoff:
+        raise SystemExit("    --cutoff must be a number.")
+    if not 1 <= args.rows <= 4096:
+        raise SystemExit("    --rows must be in 1..4096.")
+    _need_bed(args.data_path, "king names the samples through a .fam file")
+    fam = _fam_ids(args.data_path)                          # before the GPU check and before any genotype is read
+    check_unique_samples(fam, str(Path(args.data_path).with_suffix(".fam")))
+    keep = _extract_keep(args.data_path, args.extract)
+    samples = _sample_keep(args)
+    if samples is not None:
+        fam = [s for s, k in zip(fam, samples) if k]
+    data = _read_on_gpu(args, keep, samples)
+    i, j, phi, n, hh, i0 = (v.cpu().numpy() for v in king.king_pairs(data.packed, data.M, args.cutoff, rows=args.rows))
+    kept = king.unrelated_set(data.N, i, j)
+    os.makedirs(args.save_dir, exist_ok=True)
+    stem = os.path.join(args.save_dir, f"{args.name}.king")
+    relate.write_pairs(stem, i, j, phi, n, hh, i0)
+    write_sample_list(f"{stem}.in", [s for s, k in zip(fam, kept) if k])
+    write_sample_list(f"{stem}.out", [s for s, k in zip(fam, kept) if not k])
+    log.info(f"    {len(phi)} pairs with a KING-robust kinship coefficient >= {args.cutoff:.4f} among {data.N} samples:")
+    for label, edge, count in relate.band_counts(phi):
+        log.info(f"      {label} (>= {edge:.4f}): {count}")
+    log.info(f"    {int((~kept).sum())} samples removed, {int(kept.sum())} kept: no two kept samples are related at the cutoff "
+             f"(train --keep {args.name}.king.in, then infer --refine on the whole file).")
+    log.info("    Kinship pairs and sample lists saved.")
+
+
 def _kinship_main(argv):
     """``kinship`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.kin (``i j phi n`` per related pair, 0-based
     sample indices, by i then j) and {out_name}.{k}.inbreed (one inbreeding coefficient per sample)."""
@@ -640,13 +742,15 @@ def _kinship_main(argv):
     close = int((phi_h >= relate.BANDS[2][0]).sum())
     if close:
         log.info(f"    Warning: {close} pairs are second-degree relatives or closer; related samples bias the fit "
-                 "(the model assumes unrelated samples): consider removing one sample of each pair and training again.")
+                 "(the model assumes unrelated samples): consider removing one sample of each pair and training again "
+                 "(the 'king' mode lists the samples to leave out: train --remove {name}.king.out).")
     log.info("    Kinship and inbreeding coefficients saved.")
 
 
-def _read(path, device=None, keep_on_device=False, keep=None):
-    """The genotypes as PackedGenotypes; ``keep`` (bool per SNP of the file, from --extract: BED input only) selects SNPs right after
-    the read, and everything downstream sees an ordinary PackedGenotypes of the kept ones."""
+def _read(path, device=None, keep_on_device=False, keep=None, samples=None):
+    """The genotypes as PackedGenotypes; ``samples`` (bool per sample of the file, from --keep / --remove) and then ``keep`` (bool per
+    SNP of the file, from --extract) select right after the read -- BED input only -- and everything downstream sees an ordinary
+    PackedGenotypes of the kept ones."""
     from .io import read_bed_packed, read_vcf_packed
     name = os.path.basename(path)
     if ".vcf" in name:                                   # src/snp_reader.py:103
@@ -660,6 +764,10 @@ def _read(path, device=None, keep_on_device=False, keep=None):
     log.info("    Input format is BED.")
     data = read_bed_packed(path, device, keep_on_device)
     log.info(f"    Data contains {data.N} samples and {data.M} SNPs.")
+    if samples is not None:
+        from .king import select_samples
+        data = select_samples(data, samples)
+        log.info(f"    Using the {data.N} samples of --keep / --remove.")
     if keep is not None:
         from .ld import select_snps
         data = select_snps(data, keep)
@@ -699,14 +807,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
         torch.distributed.destroy_process_group()
 
 
-_ANALYSIS_MODES = {"kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
+_ANALYSIS_MODES = {"king": _king_main, "kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
                    "pse": _pse_main, "fit": _fit_main, "pca": _pca_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "fit", "pca"), \
-        ('Please provide either the argument "train" or "infer" to choose running mode ("kinship", "prune" and "hwe" check a run\'s assumptions, '
+    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "fit", "pca"), \
+        ('Please provide either the argument "train" or "infer" to choose running mode ("king" finds relatives before a run, "kinship", "prune" and "hwe" check a run\'s assumptions, '
          '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
@@ -740,7 +848,10 @@ def main(argv=None):
                                                              # through train(host_threads=) (threadpoolctl)
         from .svd import RSVD
         keep = _extract_keep(args.data_path, args.extract)  # before any genotype is read
-        data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=(num_gpus == 1), keep=keep)   # 2-bit transpose on the GPU
+        samples = _sample_keep(args)
+        if pops is not None:                                # (one line per sample of the .fam)
+            pops = _filter_lines(pops, samples, args.pops_path)
+        data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=(num_gpus == 1), keep=keep, samples=samples)   # 2-bit transpose on the GPU
         log.info("")
         log.info("    Running SVD...")
         V = RSVD(data, data.N, data.M, args.n_components, args.seed)
@@ -754,6 +865,7 @@ def main(argv=None):
     from .model import Q_P
     from .io import write_outputs
     keep = _extract_keep(args.data_path, args.extract)      # before anything is loaded
+    samples = _sample_keep(args)
     with open(f"{args.save_dir}/{args.name}_config.json") as fb:
         cfg = json.load(fb)
     Ps = None
@@ -766,7 +878,7 @@ def main(argv=None):
     if args.precision != "highest":
         log.info(f"    Matmul precision: {args.precision} (bf16-class products in the genotype passes).")
     model.load_state_dict(sd, device=torch.device("cuda:0"), max_batch=args.batch_size, precision=args.precision)
-    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep)
+    data = _read(args.data_path, torch.device("cuda:0"), keep_on_device=True, keep=keep, samples=samples)
     eng = model.engine
     eng.pack_from_host(data)
     idx = torch.arange(data.N, dtype=torch.int32, device=eng.device)

@@ -635,6 +635,14 @@ class Engine:
         self._analysis("kinship", "use relate.kinship_pairs on one GPU from the written .P and .Q files", head=head)
         return relate.kinship_pairs(self.xp, self.M, *self._fitted(head), relate.MIN_PHI if min_phi is None else min_phi, pimin=pimin)
 
+    def king(self, min_phi: Optional[float] = None, rows: int = 1024):
+        """KING-robust kinship of the resident matrix's samples (king.king_pairs; include/nadm.h, nadm_king): ``(i, j, phi, n, hethet,
+        ibs0)``, the pairs i < j with phi >= ``min_phi`` (default: the lower edge of second-degree relatives).  It reads the genotypes
+        alone, not the model; the engine's parameters and optimiser state are left as they are."""
+        from . import king
+        self._analysis("king", "use king.king_pairs on one GPU from the genotype file")
+        return king.king_pairs(self.xp, self.M, king.MIN_PHI if min_phi is None else min_phi, rows=rows)
+
     def snp_hwe(self, head: int = 0, pimin: float = 0.0):
         """Hardy-Weinberg proportions given ancestry, per SNP of the resident matrix, from head ``head``'s P and the encoder's final
         Q (hwe.snp_hwe; include/nadm.h, nadm_snp_hwe): an ``HweResult`` with ``Z, F, Fhet, p`` (float64), ``n, Hobs`` (int32) and

@@ -298,3 +298,68 @@ def resolve_ids(bim_ids, wanted, bim_path="the .bim", list_path="the list") -> n
     if not keep.any():
         raise SystemExit(f"    {list_path} lists no SNP.")
     return keep
+
+
+# ---- sample IDs: the .fam file and lists of samples ---------------------------------------------------------------------------
+def read_fam(path) -> list:
+    """A PLINK ``.fam`` -> ``[(FID, IID)]``: the first two columns of every line, in file order; a one-column line is the IID with an
+    empty FID.  (The genotype reader takes every line of the file as a sample, so a line without a field ends the run.)"""
+    out = []
+    with open(path) as fb:
+        for ln, line in enumerate(fb, 1):
+            f = line.split()
+            if not f:
+                raise SystemExit(f"    {path}: line {ln} names no sample.")
+            out.append((f[0], f[1]) if len(f) > 1 else ("", f[0]))
+    return out
+
+
+def read_sample_list(path) -> list:
+    """A list of samples (what ``plink --keep`` / ``--remove`` read): ``(FID, IID)`` of every non-empty line ``FID IID``, ``(None,
+    IID)`` of a line that holds the IID alone; in file order."""
+    out = []
+    with open(path) as fb:
+        for line in fb:
+            f = line.split()
+            if f:
+                out.append((f[0], f[1]) if len(f) > 1 else (None, f[0]))
+    return out
+
+
+def write_sample_list(path, ids) -> None:
+    """One ``FID IID`` per line (the IID alone where the FID is empty): readable by ``read_sample_list`` and by plink."""
+    with open(path, "w") as fb:
+        for fid, iid in ids:
+            fb.write(f"{fid} {iid}\n" if fid else f"{iid}\n")
+
+
+def check_unique_samples(fam_ids, fam_path="the .fam") -> None:
+    """Ends the run, naming the first duplicate, unless every ``(FID, IID)`` of the ``.fam`` occurs once."""
+    seen = set()
+    for s in fam_ids:
+        if s in seen:
+            raise SystemExit(f"    Sample {' '.join(x for x in s if x)} occurs more than once in {fam_path}.")
+        seen.add(s)
+
+
+def resolve_samples(fam_ids, wanted, fam_path="the .fam", list_path="the list") -> np.ndarray:
+    """bool ``[N]``: the samples of the ``.fam`` that ``wanted`` (``read_sample_list``) names -- by ``(FID, IID)``, or by the IID where
+    the line holds it alone.  Non-unique IDs in the ``.fam``, a name it does not hold, and an IID alone that more than one family
+    holds end the run, naming the offender."""
+    check_unique_samples(fam_ids, fam_path)
+    by_pair = {s: i for i, s in enumerate(fam_ids)}
+    by_iid = {}
+    for i, (_, iid) in enumerate(fam_ids):
+        by_iid.setdefault(iid, []).append(i)
+    keep = np.zeros(len(fam_ids), dtype=bool)
+    for fid, iid in wanted:
+        if fid is None:
+            hits = by_iid.get(iid, [])
+            if len(hits) > 1:
+                raise SystemExit(f"    Sample {iid} of {list_path} is in more than one family of {fam_path}: name it as FID IID.")
+        else:
+            hits = [by_pair[(fid, iid)]] if (fid, iid) in by_pair else []
+        if not hits:
+            raise SystemExit(f"    Sample {' '.join(x for x in (fid, iid) if x)} of {list_path} is not in {fam_path}.")
+        keep[hits[0]] = True
+    return keep

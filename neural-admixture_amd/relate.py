@@ -145,8 +145,10 @@ def band_counts(phi) -> list:
     return out
 
 
-def write_pairs(path, i, j, phi, n) -> None:
-    """One line ``i j phi n`` per pair: integers as integers, phi with the 17 digits that read back to the same float64."""
+def write_pairs(path, i, j, phi, n, *more) -> None:
+    """One line ``i j phi n`` per pair, then one column per further integer vector of ``more``: integers as integers, phi with the 17
+    digits that read back to the same float64."""
+    ints = [np.asarray(v).tolist() for v in (n,) + more]
     with open(path, "w") as fb:
-        for a, b, p, c in zip(np.asarray(i).tolist(), np.asarray(j).tolist(), np.asarray(phi, dtype=np.float64).tolist(), np.asarray(n).tolist()):
-            fb.write(f"{a:d} {b:d} {p:.17g} {c:d}\n")
+        for a, b, p, *cs in zip(np.asarray(i).tolist(), np.asarray(j).tolist(), np.asarray(phi, dtype=np.float64).tolist(), *ints):
+            fb.write(f"{a:d} {b:d} {p:.17g} " + " ".join(f"{c:d}" for c in cs) + "\n")
