@@ -2,8 +2,8 @@
 // nadm_king): five integer counts per pair, summed over the SNP axis on v_mfma_i32_16x16x64_i8 with int32 accumulators.  Exact.
 //
 // Two launches per call, no atomics, no floating point:
-//   king_accum_kernel  one 256-thread block per (64 x 64 tile of A samples x B samples, range of 256-SNP chunks; the chunk split is
-//                      the split rule of nadm_host.h, as nadm_kinship uses it).  Wave w owns the 32 x 32 quarter (w >> 1, w & 1) of
+//   king_accum_kernel  one 256-thread block per (64 x 64 tile of A samples x B samples, range of 256-SNP chunks: the scaffolding of
+//                      nadm_chunk_ranges.h, as nadm_kinship uses it).  Wave w owns the 32 x 32 quarter (w >> 1, w & 1) of
 //                      the tile: two 16-sample A tiles against two 16-sample B tiles.  The matrix is sample-major and the SNP axis
 //                      is the instruction's k, so nothing is transposed: lane l is sample l & 15 of each of its four 16-sample
 //                      tiles and k-group q = l >> 4 of the instruction, for the A and for the B operand alike (the lane -> (row, k)
@@ -29,14 +29,13 @@
 //                      per step instead of the five of a 1 x 4 layout.
 //                      SNPs >= M, the pad fields of a row's last byte, the bytes behind it and rows past the list are overwritten
 //                      with the missing code (all ones) BEFORE the expansion: they contribute exactly 0 to every count.
-//   king_fold_kernel   one thread per pair: the ranges' int32 partials in range order.
-#include "nadm_common.h"
-#include "nadm_host.h"
+//   pair_fold_kernel   (nadm_chunk_ranges.h, with KingSum) one thread per pair: the ranges' int32 partials in range order.
+#include "nadm_chunk_ranges.h"
 
 namespace nadm {
 
-constexpr int KING_CHUNK = 256;                  // SNPs per chunk = 64 bytes of a packed row
-constexpr int KING_TILE = 64;                    // samples per tile side
+constexpr int KING_CHUNK = RANGE_CHUNK;
+constexpr int KING_TILE = PAIR_TILE;             // samples per tile side
 constexpr int64_t KING_MAX_CHUNKS = 1ll << 23;   // chunks per range at most: an int32 count covers 2^31 SNPs
 constexpr int64_t KING_BLOCKS = 512;             // blocks wanted at least, while there are chunks to split (as nadm_kinship)
 constexpr int KING_COUNTS = 5;                   // n, hethet, ibs0, het_a, het_b
@@ -70,8 +69,7 @@ __global__ __launch_bounds__(256, 2) void king_accum_kernel(const uint8_t* __res
     const int r = lane & 15, q = lane >> 4;
     const int tile = (int)blockIdx.x / ranges, range = (int)blockIdx.x - tile * ranges;
     const int ta = tile / tiles_b, tb = tile - ta * tiles_b;
-    const int64_t c_lo = (int64_t)range * chunks_per_range;       // < chunks: ranges = ceil(chunks / chunks_per_range)
-    const int64_t c_hi = min(c_lo + chunks_per_range, chunks);
+    const auto [c_lo, c_hi] = chunk_range(range, chunks_per_range, chunks);
 
     // the lane's four samples: A tiles 0, 1 then B tiles 0, 1 of the wave's quarter
     const uint8_t* xrow[4];
@@ -80,18 +78,14 @@ __global__ __launch_bounds__(256, 2) void king_accum_kernel(const uint8_t* __res
     for (int i = 0; i < 4; ++i) {
         const bool isA = i < 2;
         const int pos = (isA ? ta : tb) * KING_TILE + 32 * (isA ? (w >> 1) : (w & 1)) + 16 * (i & 1) + r;
-        const int nb = isA ? ba : bb;
-        gone[i] = ~lt_mask(pos, nb);
-        const int posc = min(pos, nb - 1);
-        const int32_t* idx = isA ? idxA : idxB;
-        const int64_t row = idx ? idx[posc] : posc;
-        xrow[i] = xp + row * ld;
+        const RangeRow rr = range_row(xp, ld, isA ? idxA : idxB, pos, isA ? ba : bb);
+        xrow[i] = rr.x;
+        gone[i] = ~rr.valid;
     }
-    // a 16-byte piece past the row's end holds SNPs >= M only (4 ld >= M): its offset is clamped, every field is overwritten below
+    // (a clamped piece holds SNPs >= M only: every field of it is overwritten below)
     auto load_chunk = [&](const int64_t c, u32x4_t (&xv)[4]) {
-        const int64_t off = min(c * (KING_CHUNK / 4) + 16 * q, ld - 16);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) xv[i] = *reinterpret_cast<const u32x4_t*>(xrow[i] + off);
+        for (int i = 0; i < 4; ++i) xv[i] = range_piece(xrow[i], c, q, ld);
     };
 
     i32x4_t acc[2][2][KING_COUNTS];
@@ -154,34 +148,20 @@ __global__ __launch_bounds__(256, 2) void king_accum_kernel(const uint8_t* __res
             }
 }
 
-// One thread per pair (a < ba, b < bb): the ranges' partials in range order
-__global__ __launch_bounds__(256) void king_fold_kernel(const int32_t* __restrict__ part, const int ranges, const int tiles,
-                                                        const int tiles_b, const int ba, const int bb, int32_t* __restrict__ counts) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t pairs = (int64_t)ba * bb;
-    if (e >= pairs) return;
-    const int a = (int)(e / bb), b = (int)(e - (int64_t)a * bb);
-    const int tile = (a / KING_TILE) * tiles_b + b / KING_TILE;
-    const int o = (a % KING_TILE) * KING_TILE + b % KING_TILE;
-    int s[KING_COUNTS];
+// pair_fold_kernel's sums: the five counts, int32
+struct KingSum {
+    using Out = int32_t*;
+    Out counts;
+    int s[KING_COUNTS] = {};
+    __device__ __forceinline__ void add(const int plane, const int32_t v) { s[plane] += v; }
+    __device__ __forceinline__ void store(const int64_t e, const int64_t pairs) const {
 #pragma unroll
-    for (int k = 0; k < KING_COUNTS; ++k) s[k] = 0;
-    for (int rg = 0; rg < ranges; ++rg) {
-        const int32_t* p = part + ((int64_t)rg * tiles + tile) * KING_SLAB + o;
-#pragma unroll
-        for (int k = 0; k < KING_COUNTS; ++k) s[k] += p[k * KING_TILE * KING_TILE];
+        for (int k = 0; k < KING_COUNTS; ++k) counts[k * pairs + e] = s[k];
     }
-#pragma unroll
-    for (int k = 0; k < KING_COUNTS; ++k) counts[k * pairs + e] = s[k];
-}
+};
 
-static int64_t king_chunks(int64_t M) { return (M + KING_CHUNK - 1) / KING_CHUNK; }
-static int64_t king_tiles(int ba, int bb) { return (int64_t)((ba + KING_TILE - 1) / KING_TILE) * ((bb + KING_TILE - 1) / KING_TILE); }
-
-// chunks per range, a rule of (ba, bb, M) alone: the split rule of nadm_host.h over the chunk axis
-static int64_t king_chunks_per_range(int ba, int bb, int64_t M) {
-    return split_per_part(king_chunks(M), king_tiles(ba, bb), KING_BLOCKS, KING_MAX_CHUNKS);
-}
+// the launch shape, a rule of (ba, bb, M) alone
+static RangePlan king_plan(int ba, int bb, int64_t M) { return range_plan(M, range_tiles(ba, KING_TILE, bb, KING_TILE), KING_BLOCKS, KING_MAX_CHUNKS); }
 static bool king_shape_ok(int ba, int bb, int64_t M) {
     return ba > 0 && bb > 0 && ba <= NADM_KING_MAX_ROWS && bb <= NADM_KING_MAX_ROWS && M > 0 && M < (1ll << 31);
 }
@@ -190,16 +170,11 @@ static bool king_shape_ok(int ba, int bb, int64_t M) {
 
 using namespace nadm;
 
-extern "C" int32_t nadm_king_ranges(int32_t ba, int32_t bb, int64_t M) {
-    if (!king_shape_ok(ba, bb, M)) return 0;
-    const int64_t cpr = king_chunks_per_range(ba, bb, M);
-    return (int32_t)((king_chunks(M) + cpr - 1) / cpr);            // <= chunks < 2^23
-}
+extern "C" int32_t nadm_king_ranges(int32_t ba, int32_t bb, int64_t M) { return king_shape_ok(ba, bb, M) ? range_count(king_plan(ba, bb, M).ranges) : 0; }
 
 // scratch: [ranges][tiles][n | hethet | ibs0 | het_a | het_b][64 x 64] int32
 extern "C" int64_t nadm_king_scratch_ints(int32_t ba, int32_t bb, int64_t M) {
-    if (!king_shape_ok(ba, bb, M)) return 0;
-    return split_blocks_bound(king_chunks(M), king_tiles(ba, bb), KING_BLOCKS, KING_MAX_CHUNKS) * KING_SLAB;
+    return king_shape_ok(ba, bb, M) ? king_plan(ba, bb, M).blocks_bound * KING_SLAB : 0;
 }
 
 extern "C" int nadm_king(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
@@ -212,16 +187,12 @@ extern "C" int nadm_king(const uint8_t* xp, int64_t ld, const int32_t* idxA, int
     if ((((uintptr_t)xp | (uintptr_t)scratch) & 15) != 0) return fail("nadm_king: xp and scratch must be 16-byte aligned");
     if ((((uintptr_t)idxA | (uintptr_t)idxB | (uintptr_t)counts) & 3) != 0)
         return fail("nadm_king: idxA, idxB and counts must be 4-byte aligned");
-    const int64_t chunks = king_chunks(M), tiles = king_tiles(ba, bb);
-    const int64_t cpr = king_chunks_per_range(ba, bb, M);
-    const int64_t ranges = (chunks + cpr - 1) / cpr;
-    if (tiles * ranges > 0x7FFFFFFFll) return fail("nadm_king: too many blocks for one launch");
-    const int tiles_b = (bb + KING_TILE - 1) / KING_TILE;
+    const RangePlan pl = king_plan(ba, bb, M);
+    if (range_launch_check("nadm_king", pl)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(king_accum_kernel, dim3((unsigned)(tiles * ranges)), dim3(256), 0, st, xp, ld, idxA, ba, idxB, bb, M, tiles_b,
-                       (int)ranges, cpr, chunks, scratch);
+    hipLaunchKernelGGL(king_accum_kernel, range_grid(pl), dim3(256), 0, st, xp, ld, idxA, ba, idxB, bb, M, (bb + KING_TILE - 1) / KING_TILE,
+                       (int)pl.ranges, pl.cpr, pl.chunks, scratch);
     if (int e = check_launch("king (accumulate)")) return e;
-    hipLaunchKernelGGL(king_fold_kernel, dim3((unsigned)(((int64_t)ba * bb + 255) / 256)), dim3(256), 0, st, scratch, (int)ranges,
-                       (int)tiles, tiles_b, ba, bb, counts);
+    launch_pair_fold<int32_t, KING_COUNTS, KingSum>(scratch, pl, ba, bb, counts, st);
     return check_launch("king (fold)");
 }

@@ -14,14 +14,14 @@
 //                         A rows 16 w .. 16 w + 15 against the four 16-sample B tiles: 7 instructions per tile (hi.hi + hi.lo + lo.hi
 //                         for num and for den, one for n) into fp32 accumulators that live for the whole range.  The operand image
 //                         never leaves LDS.  Missing calls, SNPs >= M, rows past the list and masked pi enter as exactly +0.0f.
-//   kinship_fold_kernel   one thread per pair: the ranges' partials in range order in float64; n as int32.
-#include "nadm_common.h"
-#include "nadm_host.h"
+//   pair_fold_kernel      (with KinshipSum) one thread per pair: the ranges' partials in range order in float64; n as int32.
+// The chunk split, the row lookup, the clamped piece load and the fold are those of nadm_chunk_ranges.h.
+#include "nadm_chunk_ranges.h"
 
 namespace nadm {
 
-constexpr int KIN_CHUNK = 256;            // SNPs per chunk = 64 bytes of a packed row
-constexpr int KIN_TILE = 64;              // samples per tile side
+constexpr int KIN_CHUNK = RANGE_CHUNK;
+constexpr int KIN_TILE = PAIR_TILE;       // samples per tile side
 constexpr int KIN_STEP = 32;              // SNPs per build / multiply step = K of the instruction
 constexpr int KIN_MAX_CHUNKS = 1024;      // chunks per range at most: no fp32 accumulator covers more than 2^18 SNPs (n exact: < 2^24)
 constexpr int64_t KIN_BLOCKS = 512;       // blocks wanted at least (256 CUs x 2 blocks of 4 waves), while there are chunks to split
@@ -39,20 +39,14 @@ __global__ __launch_bounds__(256, KP <= 16 ? 2 : 1) void kinship_accum_kernel(
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int tile = (int)blockIdx.x / ranges, range = (int)blockIdx.x - tile * ranges;
     const int ta = tile / tiles_b, tb = tile - ta * tiles_b;
-    const int64_t c_lo = (int64_t)range * chunks_per_range;       // < chunks: ranges = ceil(chunks / chunks_per_range)
-    const int64_t c_hi = min(c_lo + chunks_per_range, chunks);
+    const auto [c_lo, c_hi] = chunk_range(range, chunks_per_range, chunks);
 
     // builder role: sample s of the 128 (A rows of the tile, then B rows), groups g0 and g0 + 2 of every step
     const int s = t & 127, g0 = t >> 7;
     const bool isA = s < KIN_TILE;
     const int pos = (isA ? ta : tb) * KIN_TILE + (s & (KIN_TILE - 1));      // position in the list
-    const int nb = isA ? ba : bb;
-    const uint32_t svalid = lt_mask(pos, nb);                     // a row past the list: every call missing
-    const int posc = min(pos, nb - 1);
-    const int32_t* idx = isA ? idxA : idxB;
-    const int64_t row = idx ? idx[posc] : posc;
-    const uint8_t* xrow = xp + row * ld;
-    const float* qrow = (isA ? QA : QB) + (int64_t)posc * q_stride;
+    const RangeRow rr = range_row(xp, ld, isA ? idxA : idxB, pos, isA ? ba : bb);      // (a row past the list: every call missing)
+    const float* qrow = (isA ? QA : QB) + (int64_t)rr.posc * q_stride;
     float q[WIDE ? 4 : KP];
     if constexpr (!WIDE) {
 #pragma unroll
@@ -67,10 +61,9 @@ __global__ __launch_bounds__(256, KP <= 16 ? 2 : 1) void kinship_accum_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) accN[i] = accD[i] = accC[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-    // a 16-byte piece past the row's end holds SNPs >= M only (4 ld >= M): its offset is clamped and the load is unconditional
     auto load_chunk = [&](const int64_t c, u32x4_t (&xv)[4]) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) xv[i] = *reinterpret_cast<const u32x4_t*>(xrow + min(c * (KIN_CHUNK / 4) + 16 * i, ld - 16));
+        for (int i = 0; i < 4; ++i) xv[i] = range_piece(rr.x, c, i, ld);
     };
     u32x4_t nxt[4];
     load_chunk(c_lo, nxt);
@@ -122,7 +115,7 @@ __global__ __launch_bounds__(256, KP <= 16 ? 2 : 1) void kinship_accum_kernel(
                 for (int e = 0; e < 8; ++e) {
                     const uint32_t code = (bits >> (2 * e)) & 3u;
                     uint32_t m = obs_mask(code);
-                    m &= svalid & lt_mask(e, rem) & ge0_mask(pi[e] - pimin) & ge0_mask(one_m_pimin - pi[e]);
+                    m &= rr.valid & lt_mask(e, rem) & ge0_mask(pi[e] - pimin) & ge0_mask(one_m_pimin - pi[e]);
                     mv[e] = m;
                     dv[e] = keepf((float)code - 2.f * pi[e], m);
                     sv[e] = keepf(__builtin_amdgcn_sqrtf(fmaxf(pi[e] * (1.f - pi[e]), 0.f)), m);
@@ -183,35 +176,22 @@ __global__ __launch_bounds__(256, KP <= 16 ? 2 : 1) void kinship_accum_kernel(
         }
 }
 
-// One thread per pair (a < ba, b < bb): the ranges' partials in range order, in float64
-__global__ __launch_bounds__(256) void kinship_fold_kernel(const float* __restrict__ part, const int ranges, const int tiles,
-                                                           const int tiles_b, const int ba, const int bb, double* __restrict__ num,
-                                                           double* __restrict__ den, int32_t* __restrict__ nobs) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)ba * bb) return;
-    const int a = (int)(e / bb), b = (int)(e - (int64_t)a * bb);
-    const int tile = (a / KIN_TILE) * tiles_b + b / KIN_TILE;
-    const int o = (a % KIN_TILE) * KIN_TILE + b % KIN_TILE;
+// pair_fold_kernel's sums: num and den in float64 (each fp32 partial cast before the add), n as an integer
+struct KinshipSum {
+    struct Out { double *num, *den; int32_t* nobs; } out;
     double ns = 0.0, ds = 0.0;
     int n = 0;
-    for (int r = 0; r < ranges; ++r) {
-        const float* p = part + ((int64_t)r * tiles + tile) * (3 * KIN_TILE * KIN_TILE) + o;
-        ns += (double)p[0];
-        ds += (double)p[KIN_TILE * KIN_TILE];
-        n += (int)p[2 * KIN_TILE * KIN_TILE];
+    __device__ __forceinline__ void add(const int plane, const float v) {
+        if (plane == 0) ns += (double)v; else if (plane == 1) ds += (double)v; else n += (int)v;
     }
-    num[e] = ns;
-    den[e] = ds;
-    if (nobs) nobs[e] = n;
-}
+    __device__ __forceinline__ void store(const int64_t e, int64_t) const {
+        out.num[e] = ns; out.den[e] = ds;
+        if (out.nobs) out.nobs[e] = n;
+    }
+};
 
-static int64_t kin_chunks(int64_t M) { return (M + KIN_CHUNK - 1) / KIN_CHUNK; }
-static int64_t kin_tiles(int ba, int bb) { return (int64_t)((ba + KIN_TILE - 1) / KIN_TILE) * ((bb + KIN_TILE - 1) / KIN_TILE); }
-
-// chunks per range, a rule of (ba, bb, M) alone: the split rule of nadm_host.h over the chunk axis
-static int64_t kin_chunks_per_range(int ba, int bb, int64_t M) {
-    return split_per_part(kin_chunks(M), kin_tiles(ba, bb), KIN_BLOCKS, KIN_MAX_CHUNKS);
-}
+// the launch shape, a rule of (ba, bb, M) alone
+static RangePlan kin_plan(int ba, int bb, int64_t M) { return range_plan(M, range_tiles(ba, KIN_TILE, bb, KIN_TILE), KIN_BLOCKS, KIN_MAX_CHUNKS); }
 static bool kin_shape_ok(int ba, int bb, int64_t M) {
     return ba > 0 && bb > 0 && ba <= NADM_KINSHIP_MAX_ROWS && bb <= NADM_KINSHIP_MAX_ROWS && M > 0;
 }
@@ -220,17 +200,11 @@ static bool kin_shape_ok(int ba, int bb, int64_t M) {
 
 using namespace nadm;
 
-extern "C" int32_t nadm_kinship_ranges(int32_t ba, int32_t bb, int64_t M) {
-    if (!kin_shape_ok(ba, bb, M)) return 0;
-    const int64_t cpr = kin_chunks_per_range(ba, bb, M);
-    const int64_t r = (kin_chunks(M) + cpr - 1) / cpr;
-    return r > 0x7FFFFFFFll ? 0 : (int32_t)r;
-}
+extern "C" int32_t nadm_kinship_ranges(int32_t ba, int32_t bb, int64_t M) { return kin_shape_ok(ba, bb, M) ? range_count(kin_plan(ba, bb, M).ranges) : 0; }
 
 // scratch: [ranges][tiles][num | den | n][64 x 64] float
 extern "C" int64_t nadm_kinship_scratch_floats(int32_t ba, int32_t bb, int64_t M) {
-    if (!kin_shape_ok(ba, bb, M)) return 0;
-    return split_blocks_bound(kin_chunks(M), kin_tiles(ba, bb), KIN_BLOCKS, KIN_MAX_CHUNKS) * (3 * KIN_TILE * KIN_TILE);
+    return kin_shape_ok(ba, bb, M) ? kin_plan(ba, bb, M).blocks_bound * (3 * KIN_TILE * KIN_TILE) : 0;
 }
 
 extern "C" int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
@@ -245,21 +219,17 @@ extern "C" int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, 
         return fail("nadm_kinship: xp, P, QA, QB and scratch must be 16-byte aligned");
     if ((((uintptr_t)num | (uintptr_t)den) & 7) != 0 || ((uintptr_t)nobs & 3) != 0)
         return fail("nadm_kinship: num, den must be 8-byte and nobs 4-byte aligned");
-    const int64_t chunks = kin_chunks(M), tiles = kin_tiles(ba, bb);
-    const int64_t cpr = kin_chunks_per_range(ba, bb, M);
-    const int64_t ranges = (chunks + cpr - 1) / cpr;
-    if (tiles * ranges > 0x7FFFFFFFll || cpr > 0x7FFFFFFFll) return fail("nadm_kinship: too many blocks for one launch");
+    const RangePlan pl = kin_plan(ba, bb, M);
+    if (range_launch_check("nadm_kinship", pl)) return 1;
     const int tiles_b = (bb + KIN_TILE - 1) / KIN_TILE;
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)(tiles * ranges);
     const float ome = 1.f - pimin;
     if (int e = dispatch_kp("nadm_kinship", kp, [&](auto KP) {
-            hipLaunchKernelGGL((kinship_accum_kernel<decltype(KP)::value>), dim3(grid), dim3(256), 0, st, xp, ld, idxA, ba, idxB, bb, M, P, QA,
-                               QB, q_stride, pimin, ome, tiles_b, (int)ranges, (int)cpr, chunks, scratch);
+            hipLaunchKernelGGL((kinship_accum_kernel<decltype(KP)::value>), range_grid(pl), dim3(256), 0, st, xp, ld, idxA, ba, idxB, bb, M, P, QA,
+                               QB, q_stride, pimin, ome, tiles_b, (int)pl.ranges, (int)pl.cpr, pl.chunks, scratch);
         }))
         return e;
     if (int e = check_launch("kinship (accumulate)")) return e;
-    hipLaunchKernelGGL(kinship_fold_kernel, dim3((unsigned)(((int64_t)ba * bb + 255) / 256)), dim3(256), 0, st, scratch, (int)ranges,
-                       (int)tiles, tiles_b, ba, bb, num, den, nobs);
+    launch_pair_fold<float, 3, KinshipSum>(scratch, pl, ba, bb, {num, den, nobs}, st);
     return check_launch("kinship (fold)");
 }

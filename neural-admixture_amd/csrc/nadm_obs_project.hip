@@ -21,11 +21,14 @@
 //                         calls of all four tiles.  Per step, SNP tile and 16 columns three instructions each into the O1 and the O2
 //                         accumulator.  Rows past the list are code 3 and their Yin rows zero; SNPs >= M are computed and never folded.
 //   the two fold kernels  one thread per output: the ranges' / slices' partials in order in float64, rounded to fp32 once; pad columns 0.
+// The forward product's range split, row lookup and clamped piece load are those of nadm_chunk_ranges.h; the transposed product's
+// slices are those of nadm_snp_sweep.h.
+#include "nadm_chunk_ranges.h"
 #include "nadm_snp_sweep.h"
 
 namespace nadm {
 
-constexpr int OBS_CHUNK = 256;            // SNPs per chunk = 64 bytes of a packed row
+constexpr int OBS_CHUNK = RANGE_CHUNK;
 constexpr int OBS_ROWS = 256;             // samples per block of the forward product: 4 waves x OBS_RT row tiles of 16
 constexpr int OBS_RT = 4;
 constexpr int OBS_STAGE = 4;              // steps of 32 SNPs whose W fragments are in LDS at a time
@@ -73,25 +76,20 @@ __global__ __launch_bounds__(256) void obs_project_kernel(const uint8_t* __restr
     __shared__ __attribute__((aligned(16))) u32x4_t Img[2 * 3 * FR];      // [matrix][piece][step][q][column]
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, r = lane & 15, q = lane >> 4;
     const int range = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - range * tiles;
-    const int64_t c_lo = (int64_t)range * chunks_per_range;       // < chunks: ranges = ceil(chunks / chunks_per_range)
-    const int64_t c_hi = min(c_lo + chunks_per_range, chunks);
+    const auto [c_lo, c_hi] = chunk_range(range, chunks_per_range, chunks);
 
     // A role: row r of row tile rt of wave w, k group q
     const uint8_t* xrow[OBS_RT];
     uint32_t inval[OBS_RT];                                       // a row past the list: every call missing
 #pragma unroll
     for (int rt = 0; rt < OBS_RT; ++rt) {
-        const int pos = tile * OBS_ROWS + 64 * w + 16 * rt + r;
-        inval[rt] = ~lt_mask(pos, b);
-        const int posc = min(pos, b - 1);
-        const int64_t row = idx ? idx[posc] : posc;
-        xrow[rt] = xp + row * ld;
+        const RangeRow rr = range_row(xp, ld, idx, tile * OBS_ROWS + 64 * w + 16 * rt + r, b);
+        xrow[rt] = rr.x;
+        inval[rt] = ~rr.valid;
     }
-    // a 16-byte piece past the row's end holds SNPs >= M only (4 ld >= M): its offset is clamped and the load is unconditional
     auto load_x = [&](const int64_t c, u32x4_t (&xv)[OBS_RT]) {
-        const int64_t off = min(c * (OBS_CHUNK / 4) + 16 * q, ld - 16);
 #pragma unroll
-        for (int rt = 0; rt < OBS_RT; ++rt) xv[rt] = *reinterpret_cast<const u32x4_t*>(xrow[rt] + off);
+        for (int rt = 0; rt < OBS_RT; ++rt) xv[rt] = range_piece(xrow[rt], c, q, ld);
     };
     // builder role: pair v is matrix x >> 4, step x >> 2 & 3 of the stage, k group x & 3 and column f % CP, f = t + 256 v, x = f / CP
     auto w_j0 = [&](const int v, const int64_t c, const int half) {
@@ -328,12 +326,10 @@ __global__ __launch_bounds__(256) void obs_project_t_fold_kernel(const float* __
     O2[e] = c < C ? (float)s2 : 0.f;
 }
 
-static int64_t obs_chunks(int64_t M) { return (M + OBS_CHUNK - 1) / OBS_CHUNK; }
-static int64_t obs_tiles(int b) { return (b + OBS_ROWS - 1) / OBS_ROWS; }
 static bool obs_shape_ok(int b, int64_t M) { return b > 0 && b <= NADM_OBS_MAX_ROWS && M > 0; }
 static bool obs_cp_ok(int CP) { return CP == 16 || CP == 32; }
-// chunks per range, a rule of (b, M) alone: the split rule of nadm_host.h over the chunk axis
-static int64_t obs_chunks_per_range(int b, int64_t M) { return split_per_part(obs_chunks(M), obs_tiles(b), OBS_BLOCKS, OBS_MAX_CHUNKS); }
+// the forward product's launch shape, a rule of (b, M) alone
+static RangePlan obs_plan(int b, int64_t M) { return range_plan(M, range_tiles(b, OBS_ROWS), OBS_BLOCKS, OBS_MAX_CHUNKS); }
 
 static int obs_check(const char* who, const void* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, int32_t C, int32_t CP) {
     if (b <= 0 || M <= 0) return failf(who, "empty block (need b > 0 and M > 0)");
@@ -349,23 +345,12 @@ static int obs_check(const char* who, const void* xp, int64_t ld, const int32_t*
 
 using namespace nadm;
 
-extern "C" int32_t nadm_obs_project_chunks(int32_t b, int64_t M) {
-    if (!obs_shape_ok(b, M)) return 0;
-    const int64_t cpr = obs_chunks_per_range(b, M);
-    return cpr > 0x7FFFFFFFll ? 0 : (int32_t)cpr;
-}
-
-extern "C" int32_t nadm_obs_project_ranges(int32_t b, int64_t M) {
-    if (!obs_shape_ok(b, M)) return 0;
-    const int64_t cpr = obs_chunks_per_range(b, M);
-    const int64_t r = (obs_chunks(M) + cpr - 1) / cpr;
-    return r > 0x7FFFFFFFll ? 0 : (int32_t)r;
-}
+extern "C" int32_t nadm_obs_project_chunks(int32_t b, int64_t M) { return obs_shape_ok(b, M) ? range_count(obs_plan(b, M).cpr) : 0; }
+extern "C" int32_t nadm_obs_project_ranges(int32_t b, int64_t M) { return obs_shape_ok(b, M) ? range_count(obs_plan(b, M).ranges) : 0; }
 
 // scratch: [ranges][256 tiles][CP] float
 extern "C" int64_t nadm_obs_project_scratch_floats(int32_t b, int64_t M, int32_t CP) {
-    if (!obs_shape_ok(b, M) || !obs_cp_ok(CP)) return 0;
-    return split_blocks_bound(obs_chunks(M), obs_tiles(b), OBS_BLOCKS, OBS_MAX_CHUNKS) * (OBS_ROWS * CP);
+    return obs_shape_ok(b, M) && obs_cp_ok(CP) ? obs_plan(b, M).blocks_bound * (OBS_ROWS * CP) : 0;
 }
 
 extern "C" int32_t nadm_obs_project_t_slices(int32_t b, int64_t M) { return obs_shape_ok(b, M) ? sweep_slices(b, M) : 0; }
@@ -382,18 +367,14 @@ extern "C" int nadm_obs_project(const uint8_t* xp, int64_t ld, const int32_t* id
     if (obs_check("nadm_obs_project", xp, ld, idx, b, M, C, CP)) return 1;
     if ((((uintptr_t)W1 | (uintptr_t)W2 | (uintptr_t)Y | (uintptr_t)scratch) & 15) != 0)
         return fail("nadm_obs_project: W1, W2, Y and scratch must be 16-byte aligned");
-    const int64_t chunks = obs_chunks(M), tiles = obs_tiles(b), cpr = obs_chunks_per_range(b, M);
-    const int64_t ranges = (chunks + cpr - 1) / cpr;
-    if (tiles * ranges > 0x7FFFFFFFll || cpr > 0x7FFFFFFFll) return fail("nadm_obs_project: too many blocks for one launch");
+    const RangePlan pl = obs_plan(b, M);
+    if (range_launch_check("nadm_obs_project", pl)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)(tiles * ranges);
-    if (CP == 16)
-        hipLaunchKernelGGL((obs_project_kernel<16>), dim3(grid), dim3(256), 0, st, xp, ld, idx, b, M, W1, W2, (int)tiles, (int)cpr, chunks, scratch);
-    else
-        hipLaunchKernelGGL((obs_project_kernel<32>), dim3(grid), dim3(256), 0, st, xp, ld, idx, b, M, W1, W2, (int)tiles, (int)cpr, chunks, scratch);
+    auto accum = CP == 16 ? obs_project_kernel<16> : obs_project_kernel<32>;
+    hipLaunchKernelGGL(accum, range_grid(pl), dim3(256), 0, st, xp, ld, idx, b, M, W1, W2, (int)pl.tiles, (int)pl.cpr, pl.chunks, scratch);
     if (int e = check_launch("obs_project (accumulate)")) return e;
-    hipLaunchKernelGGL(obs_project_fold_kernel, dim3((unsigned)(((int64_t)b * CP + 255) / 256)), dim3(256), 0, st, scratch, (int)ranges,
-                       tiles * OBS_ROWS, b, C, CP, Y);
+    hipLaunchKernelGGL(obs_project_fold_kernel, fold_grid((int64_t)b * CP), dim3(256), 0, st, scratch, (int)pl.ranges, pl.tiles * OBS_ROWS, b, C,
+                       CP, Y);
     return check_launch("obs_project (fold)");
 }
 

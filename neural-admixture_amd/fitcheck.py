@@ -30,6 +30,7 @@ import torch
 
 from ._lib import lib, check, ptr
 from ._packed import check_packed, model_operands, n_rows, stream
+from ._pairs import block_rows, walk
 
 EPS = 1e-6           # clip of pi and of 1 - pi: the projection's (project.EPS)
 ROWS = 1024          # rows per block side
@@ -139,9 +140,7 @@ def em_gap(Pp: torch.Tensor, B: torch.Tensor, C: torch.Tensor, K: int) -> float:
 
 def _resid_cor(xp, M, P, Q, idx, pairs_idx, rows, eps):
     _check_width(P, "resid_cor")
-    M, rows = int(M), int(rows)
-    if rows < 1 or rows > MAX_ROWS:
-        raise RuntimeError("rows must be in 1..4096")
+    M, rows = int(M), block_rows(rows)                          # (refused before the matrix is looked at)
     N, K, Pp, Qp = model_operands(xp, M, idx, P, Q, what="resid_cor")
     dev = xp.device
     if pairs_idx is None:
@@ -154,17 +153,14 @@ def _resid_cor(xp, M, P, Q, idx, pairs_idx, rows, eps):
     B, C = _em_sums_padded(xp, M, K, Pp, Qp, idx, N, eps)       # once, over ALL rows of the fit
     mrows = (idx.to(torch.int64)[pos] if idx is not None else pos).to(torch.int32).contiguous()     # matrix rows of the pairs' samples
     Qs = Qp[pos].contiguous()
-    rows = min(rows, S_)
+    rows, blocks = walk(S_, rows, mrows, dev, ordered=True)     # ALL ordered blocks: c_ab and c_ba are different computations
     scratch = resid_cor_scratch(rows, rows, M, int(Pp.shape[1]), dev)
     c = torch.empty((S_, S_), dtype=torch.float64, device=dev)
     n = torch.empty((S_, S_), dtype=torch.int32, device=dev)
-    for a in range(0, S_, rows):                                # ALL ordered blocks: c_ab and c_ba are different computations
-        ba = min(rows, S_ - a)
-        for b in range(0, S_, rows):
-            bb = min(rows, S_ - b)
-            Sab, Ta, Tb, nn = resid_cor_block(xp, M, Pp, K, mrows[a:a + ba], Qs[a:a + ba], mrows[b:b + bb], Qs[b:b + bb], B, C, eps, scratch)
-            c[a:a + ba, b:b + bb] = _cor(Sab, Ta, Tb)
-            n[a:a + ba, b:b + bb] = nn
+    for a, ba, ia, b, bb, ib in blocks:
+        Sab, Ta, Tb, nn = resid_cor_block(xp, M, Pp, K, ia, Qs[a:a + ba], ib, Qs[b:b + bb], B, C, eps, scratch)
+        c[a:a + ba, b:b + bb] = _cor(Sab, Ta, Tb)
+        n[a:a + ba, b:b + bb] = nn
     cor = (c + c.T) * 0.5                                       # symmetric bit for bit: x + y == y + x
     cor.fill_diagonal_(float("nan"))
     return cor, n, em_gap(Pp, B, C, K)

@@ -24,6 +24,7 @@ import torch
 
 from ._lib import lib, check, ptr
 from ._packed import check_packed, n_rows, stream
+from ._pairs import PairList, mirror, walk
 
 ROWS = 1024                  # rows per block side of the dense and the pair form
 MIN_PHI = 2.0 ** -3.5        # lower edge of second-degree relatives (0.0884): plink2's customary --king-cutoff
@@ -72,20 +73,10 @@ def _blocks(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor], rows: int):
     rows a.. against the rows b.., one ``nadm_king`` call each."""
     N = n_rows(xp, idx)
     check_packed(xp, idx, N, "king")
-    rows = int(rows)
-    if rows < 1 or rows > 4096:
-        raise RuntimeError("rows must be in 1..4096")
-    rows = min(rows, N)
+    rows, blocks = walk(N, rows, idx, xp.device)
     scratch = king_scratch(rows, rows, int(M), xp.device)
-
-    def rows_of(s, b):
-        return idx[s:s + b] if idx is not None else torch.arange(s, s + b, dtype=torch.int32, device=xp.device)
-    for a in range(0, N, rows):
-        ba = min(rows, N - a)
-        ia = rows_of(a, ba)
-        for b in range(a, N, rows):
-            bb = min(rows, N - b)
-            yield a, b, king_block(xp, M, ia, rows_of(b, bb), ba, bb, scratch)
+    for a, ba, ia, b, bb, ib in blocks:
+        yield a, b, king_block(xp, M, ia, ib, ba, bb, scratch)
 
 
 def king(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor] = None, rows: int = ROWS):
@@ -95,10 +86,7 @@ def king(xp: torch.Tensor, M: int, idx: Optional[torch.Tensor] = None, rows: int
     N = n_rows(xp, idx)
     counts = torch.empty((5, N, N), dtype=torch.int32, device=xp.device)
     for a, b, c in _blocks(xp, M, idx, rows):
-        ba, bb = c.shape[1:]
-        counts[:, a:a + ba, b:b + bb] = c
-        if a != b:
-            counts[:, b:b + bb, a:a + ba] = c[[0, 1, 2, 4, 3]].transpose(1, 2)
+        mirror(counts, a, b, c, swap=[0, 1, 2, 4, 3])
     return phi_from_counts(counts), counts
 
 
@@ -107,18 +95,10 @@ def king_pairs(xp: torch.Tensor, M: int, min_phi: float = MIN_PHI, rows: int = R
     with ``phi >= min_phi`` (default: the lower edge of second-degree relatives), ordered by i then j, on xp's device.  One ``rows`` x
     ``rows`` block is held at a time: works at any N."""
     N = n_rows(xp, idx)
-    out = [[] for _ in range(6)]
+    pairs = PairList(N, min_phi)
     for a, b, c in _blocks(xp, M, idx, rows):
-        ph = phi_from_counts(c)
-        keep = ph >= min_phi                                 # (NaN compares false)
-        if a == b:
-            keep = torch.triu(keep, 1)
-        ii, jj = torch.nonzero(keep, as_tuple=True)          # row-major: by i, then j
-        for o, v in zip(out, (ii + a, jj + b, ph[ii, jj], c[0][ii, jj], c[1][ii, jj], c[2][ii, jj])):
-            o.append(v)
-    i, j, p, n, hh, i0 = (torch.cat(o) for o in out)
-    order = torch.argsort(i * N + j)                         # the blocks of one row band come one after the other
-    return i[order], j[order], p[order], n[order], hh[order], i0[order]
+        pairs.add(a, b, phi_from_counts(c), c[0], c[1], c[2])
+    return pairs.result()
 
 
 def unrelated_set(N: int, i, j) -> np.ndarray:

@@ -22,6 +22,7 @@ import torch
 
 from ._lib import lib, check, ptr
 from ._packed import check_packed, model_operands, n_rows, stream
+from ._pairs import PairList, mirror, walk
 
 ROWS = 1024                  # rows per block side of the dense and the pair form
 MIN_PHI = 2.0 ** -4.5        # lower edge of third-degree relatives (0.0442)
@@ -72,22 +73,12 @@ def _blocks(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor], rows: i
     """The ``rows`` x ``rows`` blocks of pairs with a <= b, row band by row band: yields ``(a, b, phi [ba, bb] float64, n [ba, bb]
     int32)`` of the rows a.. against the rows b.., one ``nadm_kinship`` call each."""
     check_packed(xp, idx, n_rows(xp, idx))                  # (ahead of the range of ``rows``, as the refusals have always come)
-    rows = int(rows)
-    if rows < 1 or rows > 4096:
-        raise RuntimeError("rows must be in 1..4096")
-    N, K, Pp, Qp = model_operands(xp, M, idx, P, Q)
-    rows = min(rows, N)
+    rows, blocks = walk(n_rows(xp, idx), rows, idx, xp.device)
+    _, K, Pp, Qp = model_operands(xp, M, idx, P, Q)
     scratch = kinship_scratch(rows, rows, M, xp.device)
-
-    def rows_of(s, b):
-        return idx[s:s + b] if idx is not None else torch.arange(s, s + b, dtype=torch.int32, device=xp.device)
-    for a in range(0, N, rows):
-        ba = min(rows, N - a)
-        ia = rows_of(a, ba)
-        for b in range(a, N, rows):
-            bb = min(rows, N - b)
-            num, den, nn = kinship_block(xp, M, Pp, K, ia, Qp[a:a + ba], rows_of(b, bb), Qp[b:b + bb], pimin, scratch)
-            yield a, b, _phi(num, den), nn
+    for a, ba, ia, b, bb, ib in blocks:
+        num, den, nn = kinship_block(xp, M, Pp, K, ia, Qp[a:a + ba], ib, Qp[b:b + bb], pimin, scratch)
+        yield a, b, _phi(num, den), nn
 
 
 def kinship(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor] = None, rows: int = ROWS, pimin: float = 0.0):
@@ -100,15 +91,8 @@ def kinship(xp: torch.Tensor, M: int, P, Q, idx: Optional[torch.Tensor] = None, 
     phi = torch.empty((N, N), dtype=torch.float64, device=xp.device)
     n = torch.empty((N, N), dtype=torch.int32, device=xp.device)
     for a, b, ph, nn in _blocks(xp, M, P, Q, idx, rows, pimin):
-        ba, bb = ph.shape
-        if a == b:                                           # the upper triangle of a diagonal block is the one that counts
-            ph = torch.triu(ph) + torch.triu(ph, 1).T
-            nn = torch.triu(nn) + torch.triu(nn, 1).T
-        phi[a:a + ba, b:b + bb] = ph
-        n[a:a + ba, b:b + bb] = nn
-        if a != b:
-            phi[b:b + bb, a:a + ba] = ph.T
-            n[b:b + bb, a:a + ba] = nn.T
+        mirror(phi, a, b, ph, upper=True)                    # the upper triangle of a diagonal block is the one that counts
+        mirror(n, a, b, nn, upper=True)
     return phi, n
 
 
@@ -119,20 +103,12 @@ def kinship_pairs(xp: torch.Tensor, M: int, P, Q, min_phi: float = MIN_PHI, rows
     ``2 phi_aa - 1`` of every sample, all on xp's device.  One ``rows`` x ``rows`` block is held at a time: works at any N."""
     N = n_rows(xp, idx)
     inb = torch.empty(N, dtype=torch.float64, device=xp.device)
-    out_i, out_j, out_p, out_n = [], [], [], []
+    pairs = PairList(N, min_phi)
     for a, b, ph, nn in _blocks(xp, M, P, Q, idx, rows, pimin):
-        keep = ph >= min_phi                                 # (NaN compares false)
         if a == b:
             inb[a:a + ph.shape[0]] = 2.0 * torch.diagonal(ph) - 1.0
-            keep = torch.triu(keep, 1)
-        ii, jj = torch.nonzero(keep, as_tuple=True)          # row-major: by i, then j
-        out_i.append(ii + a)
-        out_j.append(jj + b)
-        out_p.append(ph[ii, jj])
-        out_n.append(nn[ii, jj])
-    i, j, p, nn = torch.cat(out_i), torch.cat(out_j), torch.cat(out_p), torch.cat(out_n)
-    order = torch.argsort(i * N + j)                         # the blocks of one row band come one after the other
-    return i[order], j[order], p[order], nn[order], inb
+        pairs.add(a, b, ph, nn)
+    return pairs.result() + (inb,)
 
 
 def band_counts(phi) -> list:

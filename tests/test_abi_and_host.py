@@ -175,16 +175,19 @@ def test_pass3_sample_slice_rule_and_slab_sizes():
 
 
 def test_split_schedule_of_the_analysis_kernels_is_the_recorded_one():
-    """The slices, ranges and scratch sizes of project_q, project_p, snp_hwe and kinship are pure host rules of the shape.  Their values
-    over the grid of the schedule tests, and the argument lists that must return 0, were recorded (tests/golden/split_schedule.json)
-    from the library in which every entry point carried its own copy of the split rule; the shared rule (csrc/nadm_host.h:
-    split_per_part, split_blocks_bound) returns every one of them unchanged."""
+    """The slices, ranges and scratch sizes of project_q, project_p, snp_hwe, kinship, king, resid_cor and obs_project are pure host rules
+    of the shape.  Their values over the grid of the schedule tests, and the argument lists that must return 0, were recorded
+    (tests/golden/split_schedule.json) from the library in which every entry point carried its own copy of the split rule, resp. of the
+    chunk-range plan; the shared rule (csrc/nadm_host_rules.h: split_per_part, split_blocks_bound) and the shared plan
+    (csrc/nadm_chunk_ranges.h) return every one of them unchanged."""
     import itertools
     from neural_admixture_amd._lib import lib
     rec = json.load(open(os.path.join(G, "split_schedule.json")))
     names = [n for n in rec if not n.startswith("_")]
     assert sorted(names) == sorted(["nadm_project_p_slices", "nadm_project_p_scratch_floats", "nadm_snp_hwe_slices", "nadm_snp_hwe_scratch_floats",
-                                    "nadm_kinship_ranges", "nadm_kinship_scratch_floats", "nadm_project_scratch_floats"])
+                                    "nadm_kinship_ranges", "nadm_kinship_scratch_floats", "nadm_project_scratch_floats",
+                                    "nadm_king_ranges", "nadm_king_scratch_ints", "nadm_resid_cor_ranges", "nadm_resid_cor_scratch_floats",
+                                    "nadm_obs_project_chunks", "nadm_obs_project_ranges", "nadm_obs_project_scratch_floats"])
     for name in names:
         fn, r = getattr(lib, name), rec[name]
         points = list(itertools.product(*[vals for _, vals in r["axes"]]))
