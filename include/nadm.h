@@ -839,6 +839,41 @@ int nadm_snp_info(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, 
                   float eps, double* info, int32_t* nobs, float* scratch, void* stream);
 int nadm_snp_info_se(const double* info, const uint8_t* drop, const int32_t* nobs, int64_t M, int32_t k, double* se, void* stream);
 
+/* ---- Standard errors of Q given P: the per-SAMPLE Fisher information of a sample's row of ancestry fractions GIVEN the frequencies -
+ * The mirror image of nadm_snp_info: how sure is a sample's q_i. when P is held fixed -- a projected sample (nadm_project_q), whose
+ * error comes from the SNP axis: from how many of its calls were observed and how far apart the columns of P are there.  One call
+ * = the rows idx[0..b) (idx == NULL: rows 0..b; any order, a duplicate is a sample of its own), ONE head P [M, kp] (kp =
+ * nadm_pad_k(k), pad cols 0) and Q [b, k] (row s belongs to idx[s], row stride q_stride, a multiple of 4, >= kp, pad cols 0).
+ * Codes g in {0, 1, 2} are observed, 3 is missing:
+ *     pi_ij  = sum_k q_ik p_jk                                      (fp32, fused multiply-adds, k in order, as nadm_project_q)
+ *     o_ij   = 1 if the call is observed and j < M, else 0
+ *     r = clip(pi, eps, 1 - eps);   u = clip(1 - pi, eps, 1 - eps)  (u from the UNCLIPPED pi, as nadm_project_p)
+ *     w_ij   = o_ij 2 / (r u)                                       (the Fisher information of pi in one binomial(2, pi) call)
+ *     A_i[a][c] = sum_j w_ij p_ja p_jc   for a <= c < k             n_i = sum_j o_ij
+ * The EXPECTED information of the row q_i., for the reasons given at nadm_snp_info: the weight does not depend on the call's value
+ * and is bounded by 2 / eps.  The caller inverts A_i under the constraint sum_k q_ik = 1 in float64 (neural_admixture_amd/qse.py):
+ * the result is CONDITIONAL on P.  info double [b, k (k + 1) / 2]: the pairs a <= c of the real columns, a-major ((0,0), (0,1), ..,
+ * (0,k-1), (1,1), ..); nobs int32 [b].  k <= 16 (kp in {4, 8, 12, 16}): the kp (kp + 1) / 2 running sums of a sample live in one
+ * thread's registers; a wider head is refused.  eps in [1e-9, 0.5).  scratch: nadm_sample_info_scratch_floats(b, M, kp) floats (grows
+ * with b, with M and with kp; 0 for a kp without a kernel).  xp, P, Q, scratch 16-byte, info 8-byte, nobs, idx 4-byte aligned; ld >=
+ * ceil(M/4), ld % 16 == 0, ld < 2^32; the address of row r is r * ld in 64 bits.
+ * A missing call, a row past the list and a SNP >= M enter every sum as exactly +0.0f / 0: the result does not depend on the pad
+ * bits of a row's last byte, nor on the values of P at the SNPs where the sample's call is missing (P must be finite: a masked term
+ * is still multiplied by that 0); a sample without an observed call gets n = 0 and +0.0 throughout.  1 / (r u) is one multiplication
+ * and the hardware's 1-ulp reciprocal; w p_a is rounded once, then fused multiply-adds.  The 256-SNP chunks are cut into
+ * nadm_sample_info_ranges(b, M) contiguous ranges (more than one while the block's 256-sample tiles alone do not fill the chip); a
+ * lane's fp32 running sums cover one range in SNP order and never more than 2^18 SNPs (1024 chunks, as nadm_kinship and
+ * nadm_obs_project: 2^18 terms of one sign lose at most 2^18 x 2^-24 = 1.6 % in the worst case and about sqrt(2^18) x 2^-24 = 3e-5
+ * where the roundings do not line up); the ranges' partials are added in float64 in range order and the factor 2 is applied once, there (exact); n is an
+ * integer sum, exact.  The order depends on (b, M) alone and there are no floating-point atomics: the same inputs give the same
+ * bits.  Every refusal -- a null pointer, an empty batch, ld, k and kp, q_stride, eps, k > 16, alignment -- is reported before
+ * anything is launched.  Asynchronous on `stream`. */
+int32_t nadm_sample_info_ranges(int32_t b, int64_t M);
+int64_t nadm_sample_info_scratch_floats(int32_t b, int64_t M, int32_t kp);
+int nadm_sample_info(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                     const float* P, int32_t k, int32_t kp, const float* Q, int32_t q_stride,
+                     float eps, double* info, int32_t* nobs, float* scratch, void* stream);
+
 /* ---- Model-fit check: the pairwise correlation of leave-one-out residuals (evalAdmix, Garcia-Erill & Albrechtsen 2020) -----------
  * Does the model describe these samples, and if not, which ones?  Under a good fit the residuals g - 2 pi of two samples are
  * uncorrelated; where the model is wrong the correlation is positive inside the groups it merged or mis-modelled and negative

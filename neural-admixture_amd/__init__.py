@@ -17,6 +17,7 @@ from .ld import snp_counts, ld_band, prune, select_snps    # noqa: F401  (LD pru
 from .hwe import snp_hwe, snp_hwe_sums, hwe_keep    # noqa: F401  (Hardy-Weinberg score test given ancestry, per SNP, from Q and P)
 from .cv import cv_error, mask_fold, heldout_deviance    # noqa: F401  (cross-validation error for choosing K, over held-out calls)
 from .bootstrap import bootstrap_q, block_weights    # noqa: F401  (bootstrap standard errors of Q: SNPs resampled, weighted refits)
+from .qse import q_se, q_info                  # noqa: F401  (standard errors of Q given P: per-sample Fisher information, inverted under the sum constraint)
 from .pse import p_se, p_info, se_from_info    # noqa: F401  (standard errors of P: per-SNP Fisher information given Q, inverted)
 from .fitcheck import resid_cor, em_sums, fit_check, group_means, sample_means    # noqa: F401  (model-fit check: correlation of leave-one-out residuals)
 from . import pca                 # noqa: F401  (principal components of the standardised genotypes: pca.pca; the module, whose name its function shares)
@@ -25,5 +26,5 @@ from . import pack2bit            # noqa: F401  (the reference's native module b
 
 __all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish", "kinship", "kinship_pairs", "king_pairs", "unrelated_set", "select_samples",
            "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep", "cv_error", "mask_fold", "heldout_deviance",
-           "bootstrap_q", "block_weights", "p_se", "p_info", "se_from_info", "resid_cor", "em_sums", "fit_check", "group_means",
+           "bootstrap_q", "block_weights", "p_se", "p_info", "se_from_info", "q_se", "q_info", "resid_cor", "em_sums", "fit_check", "group_means",
            "sample_means", "pca", "obs_project", "obs_project_t"]

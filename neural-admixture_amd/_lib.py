@@ -125,6 +125,9 @@ def _load():
         "nadm_snp_info_scratch_floats": (i64, [i32, i64, i32]),
         "nadm_snp_info": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, i32, vp, f32, vp, vp, vp, vp]),
         "nadm_snp_info_se": (C.c_int, [vp, vp, vp, i64, i32, vp, vp]),
+        "nadm_sample_info_ranges": (i32, [i32, i64]),
+        "nadm_sample_info_scratch_floats": (i64, [i32, i64, i32]),
+        "nadm_sample_info": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, vp, i32, f32, vp, vp, vp, vp]),
         "nadm_em_sums_slices": (i32, [i32, i64]),
         "nadm_em_sums_scratch_floats": (i64, [i32, i64, i32]),
         "nadm_em_sums": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp]),

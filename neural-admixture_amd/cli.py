@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|king|kinship|prune|hwe|cv|bootstrap|pse|fit|pca ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|king|kinship|prune|hwe|cv|bootstrap|pse|qse|fit|pca ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -104,6 +104,11 @@ def parse_train_args(argv):
                    help="after training (and after --polish), standard errors of every K's P from the per-SNP Fisher information given "
                         "the Q about to be written: {name}.{K}.P_se, M x K like the .P file, nan where no standard error is defined.  "
                         "Conditional on Q; every K must be <= 16.  Single-GPU, unsupervised runs only")
+    p.add_argument("--q_se", action="store_true",
+                   help="after training (and after --polish), standard errors of every K's Q from the per-sample Fisher information given "
+                        "the P about to be written: {name}.{K}.Q_info_se, N x K like the .Q file, nan for a sample without one.  "
+                        "Conditional on P (for the training samples it leaves out P's own error; --bootstrap gives the joint one); an "
+                        "entry at 0 or 1 carries a detection limit, not a spread.  Every K must be <= 16.  Single-GPU, unsupervised runs only")
     p.add_argument("--fit_check", action="store_true",
                    help="after training (and after --polish), the model-fit check of every K from the matrices about to be written: the "
                         "pairwise correlation of leave-one-out residuals (evalAdmix's statistic), summarised per group of samples (largest "
@@ -132,6 +137,12 @@ def parse_infer_args(argv):
                         "0 (default): the encoder's Q as it is")
     p.add_argument("--refine_tol", type=float, default=1e-4,
                    help="stop refining a batch once no entry of Q moves by this much in a step")
+    p.add_argument("--q_se", action="store_true",
+                   help="with --refine: standard errors of the refined Q from the per-sample Fisher information given the fixed P, "
+                        "written next to the .Q as {out_name}.{K}.Q_info_se (N x K, nan for a sample without an observed call); a sample "
+                        "with few observed calls shows there.  An entry at 0 or 1 carries a detection limit.  Every K must be <= 16")
+    p.add_argument("--bound", type=float, default=1e-4,
+                   help="--q_se logs a fraction within this of 0 or 1 as at the bound (default 1e-4)")
     _add_precision(p)
     _add_extract(p)
     _add_samples(p)
@@ -251,6 +262,15 @@ def parse_pse_args(argv):
     _add_run_args(p, multi_k=True)
     p.add_argument("--bound", type=float, default=1e-4,
                    help="a frequency within this of 0 or 1 is taken as fixed at the boundary and gets no standard error (default 1e-4)")
+    return p.parse_args(argv)
+
+
+def parse_qse_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture qse",
+                                description="Standard errors of Q given P: the per-sample Fisher information, from a run's .P and .Q files")
+    _add_run_args(p, multi_k=True)
+    p.add_argument("--bound", type=float, default=1e-4,
+                   help="a fraction within this of 0 or 1 is counted as at the bound: its standard error is a detection limit (default 1e-4)")
     return p.parse_args(argv)
 
 
@@ -646,6 +666,24 @@ def _pse_main(argv):
     log.info("    Standard errors of P saved.")
 
 
+def _qse_main(argv):
+    """``qse`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.Q_info_se (N x K, the .Q
+    text format, nan throughout a sample without a standard error) and the ``Q standard errors given P (K=k)`` lines per K in the log."""
+    from . import qse
+    args = parse_qse_args(argv)
+    ks = _ks_asked(args)
+    _check_ks16(ks, "qse", "q_se")
+    if not 0.0 <= args.bound < 0.5:
+        raise SystemExit("    --bound must be in [0, 0.5).")
+    data, Ps, Qs = _read_run_heads(args, ks, "qse")
+    log.info(f"    Standard errors of Q given P (expected Fisher information per sample, every component free under the sum constraint; "
+             f"at the bound within {args.bound:g} of 0 or 1).")
+    results = [qse.q_se(data.packed, data.M, P, Q, bound=args.bound) for P, Q in zip(Ps, Qs)]
+    qse.log_results(results, log)
+    qse.write_results(args.save_dir, args.out_name or args.name, results)
+    log.info("    Standard errors of Q saved.")
+
+
 def _fit_main(argv):
     """``fit`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.cor_pop (a header line of
     group names, then the G x G mean correlations of leave-one-out residuals), {out_name}.{K}.cor_sample (``mean_cor n_pairs`` per
@@ -808,14 +846,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 
 _ANALYSIS_MODES = {"king": _king_main, "kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
-                   "pse": _pse_main, "fit": _fit_main, "pca": _pca_main}
+                   "pse": _pse_main, "qse": _qse_main, "fit": _fit_main, "pca": _pca_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "fit", "pca"), \
+    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "qse", "fit", "pca"), \
         ('Please provide either the argument "train" or "infer" to choose running mode ("king" finds relatives before a run, "kinship", "prune" and "hwe" check a run\'s assumptions, '
-         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes).')
+         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "qse" on Q given P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         _ANALYSIS_MODES[mode](argv[1:])
@@ -862,6 +900,11 @@ def main(argv=None):
             _train_worker(0, args, 1, data, V, pops, t0)
         return 0
     args = parse_infer_args(argv[1:])
+    if args.q_se and args.refine <= 0:                     # before anything is loaded
+        raise SystemExit("    --q_se needs --refine N: the encoder's Q is not a maximum of the likelihood given P, and the standard "
+                         "error would not belong to it.")
+    if args.q_se and not 0.0 <= args.bound < 0.5:
+        raise SystemExit("    --bound must be in [0, 0.5).")
     from .model import Q_P
     from .io import write_outputs
     keep = _extract_keep(args.data_path, args.extract)      # before anything is loaded
@@ -869,6 +912,8 @@ def main(argv=None):
     with open(f"{args.save_dir}/{args.name}_config.json") as fb:
         cfg = json.load(fb)
     Ps = None
+    if args.q_se:
+        _check_ks16(cfg["ks"], "--q_se", "q_se")
     if args.refine > 0:                                    # the training run's {name}.{k}.P, looked for before anything is loaded
         P_paths = find_run_files(args.save_dir, args.name, cfg["ks"], "P", "--refine")
     sd = torch.load(f"{args.save_dir}/{args.name}.pt", map_location="cpu", weights_only=True)
@@ -887,6 +932,9 @@ def main(argv=None):
         for h, P_MK in enumerate(Ps):
             eng.load_P(h, P_MK)
         ll0 = ll1 = 0.0
+    if args.q_se:
+        from . import qse
+        Pd, ses = [torch.as_tensor(P_MK, dtype=torch.float32).to(eng.device) for P_MK in Ps], [[] for _ in cfg["ks"]]
     for s, bb in row_ranges(data.N, args.batch_size):     # engine.final_q's ranges, with the projection of a batch in between
         qs = eng.infer_q(idx[s:s + bb], bb)
         if Ps is not None:                                 # projection: the encoder's Q is the start of the masked EM steps
@@ -894,6 +942,9 @@ def main(argv=None):
             ll0 += float(sum(ll.sum() for ll in lls))
             qs, lls, _ = eng.project_q(idx[s:s + bb], bb, q0=qs, iters=args.refine, tol=args.refine_tol, with_loglik=True)
             ll1 += float(sum(ll.sum() for ll in lls))
+            if args.q_se:                                  # at the refined Q, given the P it was refined against
+                for h, q in enumerate(qs):
+                    ses[h].append(qse.q_se(eng.xp, eng.M, Pd[h], q, idx[s:s + bb], bound=args.bound))
         for h, q in enumerate(qs):
             outs[h].append(q.cpu().numpy())
     if Ps is not None:
@@ -902,6 +953,11 @@ def main(argv=None):
     Qs = [np.concatenate(o, axis=0) for o in outs]
     K = cfg["ks"][0] if len(cfg["ks"]) == 1 else None
     write_outputs(Qs, args.out_name, K, cfg["ks"][0], cfg["ks"][-1], args.save_dir)
+    if args.q_se:
+        results = [qse.concat(r) for r in ses]
+        qse.log_results(results, log)
+        qse.write_results(args.save_dir, args.out_name, results)
+        log.info("    Standard errors of Q saved.")
     log.info(f"    Total elapsed time: {time.time() - t0:.2f} seconds.")
     return 0
 

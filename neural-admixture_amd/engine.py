@@ -662,6 +662,17 @@ class Engine:
         self._analysis("p_se", "use pse.p_se on one GPU from the written .P and .Q files", head=head, max_k=(pse.MAX_K, pse.TOO_WIDE))
         return pse.p_se(self.xp, self.M, *self._fitted(head), bound=bound)
 
+    def q_se(self, head: int = 0, bound: float = 1e-4):
+        """Standard errors of the encoder's final Q, per sample and component of the resident matrix, from the per-sample Fisher
+        information given head ``head``'s P (qse.q_se; include/nadm.h, nadm_sample_info): a ``QseResult`` with ``se`` (float64
+        ``[N, K]``, NaN throughout a sample without an observed call or with a singular block), ``n`` (int32 ``[N]``) and the
+        ``at_bound`` pattern (``q`` within ``bound`` of 0 or 1: the SE there is a detection limit).  Conditional on P, and the
+        encoder's Q is not a maximum of this likelihood: project first (``project_q``) where that matters.  K <= 16.  The engine's
+        parameters and optimiser state are left as they are."""
+        from . import qse
+        self._analysis("q_se", "use qse.q_se on one GPU from the written .P and .Q files", head=head, max_k=(qse.MAX_K, qse.TOO_WIDE))
+        return qse.q_se(self.xp, self.M, *self._fitted(head), bound=bound)
+
     def resid_cor(self, head: int = 0, pairs_idx=None, rows: int = 1024):
         """Model fit along the sample axis: the symmetrised correlation of leave-one-out residuals of the resident matrix's samples
         from head ``head``'s P and the encoder's final Q (fitcheck.resid_cor; include/nadm.h, nadm_em_sums / nadm_resid_cor):

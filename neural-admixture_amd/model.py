@@ -45,7 +45,7 @@ class Q_P:
         self.ks_list = [int(k) for k in ks_list]
         self.engine = engine
         self.full_params = full_params       # SNP-sharded runs: {"V": [M,C], "P": [[M,k] ...]} gathered on the master
-        self.after_results: dict = {}        # train(..., bootstrap / p_se / fit_check) leaves one result per head here, under the keyword
+        self.after_results: dict = {}        # train(..., bootstrap / p_se / q_se / fit_check) leaves one result per head here, under the keyword
         self._pending = None
         if engine is None and V is not None:
             self._pending = {"V": V}

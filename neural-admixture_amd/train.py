@@ -255,6 +255,7 @@ AFTER_TRAINING = (                                        # in the order they ru
     AfterOption("cv", ("cv", "cv_rounds", "cv_tol"), _check_cv, None, None),
     AfterOption("bootstrap", ("bootstrap", "boot_block", "boot_rounds", "boot_tol"), _check_bootstrap, None, "bootstrap"),
     AfterOption("p_se", ("p_se",), None, "the K (K + 1) / 2 running sums of a SNP live in one thread's registers", "pse"),
+    AfterOption("q_se", ("q_se",), None, "the K (K + 1) / 2 running sums of a sample live in one thread's registers", "qse"),
     AfterOption("fit_check", ("fit_check",), None, "a sample's Q row and a chunk's refitted frequencies live in registers and LDS",
                 "fitcheck"),
 )
@@ -266,7 +267,7 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
           n_components: int = None, *, parallelism: str = "dp", host_threads: int = 4, gmm: str = "auto", precision: str = "highest",
           unlabelled=None, supervised_loss_weight: float = 100.0, polish: int = 0, polish_tol: float = 1e-5, cv: int = 0,
           cv_rounds: int = 50, cv_tol: float = 1e-5, bootstrap: int = 0, boot_block: int = 1, boot_rounds: int = 50, boot_tol: float = 1e-5,
-          p_se: bool = False, fit_check: bool = False):
+          p_se: bool = False, q_se: bool = False, fit_check: bool = False):
     """The reference's boundary function (see the module docstring and _train).  The host thread pools (torch intra-op, BLAS,
     OpenMP) are capped at ``host_threads`` while it runs -- the reference's CLI does that with --threads (entry.py:138-146), and
     this package's CLI passes its --threads here; the epoch loop itself always runs with torch's pool at 1 (model.py).
@@ -293,6 +294,8 @@ def train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int,
     (bootstrap.bootstrap_q, draw seed ``seed``), refitted from those matrices (files: .Q_se / .Q_bias).
     ``p_se`` (keyword, CLI --p_se): the standard errors of every K's P from the per-SNP Fisher information given the Q about to be
     returned (pse.p_se; every K <= 16; file: .P_se).
+    ``q_se`` (keyword, CLI --q_se): the standard errors of every K's Q from the per-sample Fisher information given the P about to be
+    returned (qse.q_se; every K <= 16; file: .Q_info_se).  Conditional on P: for the samples P was fitted to it leaves out P's own error.
     ``fit_check`` (keyword, CLI --fit_check): the model-fit check of every K (fitcheck.fit_check: the correlation of leave-one-out
     residuals, grouped by largest component; every K <= 16; above 4096 samples the pairs of a subset drawn with ``seed``; files:
     .cor_pop / .cor_sample)."""
@@ -402,6 +405,11 @@ def _train(epochs: int, batch_size: int, learning_rate: float, K: int, seed: int
         from . import pse as _pse
         done["p_se"] = [_pse.p_se(xp, M, P_k, Q_k) for P_k, Q_k in zip(Ps, Qs)]
         _pse.log_results(done["p_se"], log)
+        log.info("")
+    if after.q_se:                                         # likewise: of the Q about to be returned, given the P about to be returned
+        from . import qse as _qse
+        done["q_se"] = [_qse.q_se(xp, M, P_k, Q_k) for P_k, Q_k in zip(Ps, Qs)]
+        _qse.log_results(done["q_se"], log)
         log.info("")
     if after.fit_check:                                    # likewise: of the P and Q about to be returned
         from . import fitcheck as _fit
