@@ -970,6 +970,49 @@ int64_t nadm_obs_project_t_scratch_floats(int32_t b, int64_t M, int32_t CP);
 int nadm_obs_project_t(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M, const float* Yin, int32_t C,
                        int32_t CP, float* O1, float* O2, float* scratch, void* stream);
 
+/* ---- Residual PCA given Q and P: the two products of the model's standardised (Pearson) residuals ---------------------------------
+ * What structure is left in the data once the K components are taken out, and which samples carry it?  nadm_resid_cor answers for
+ * pairs at O(N^2 M K); the principal components of the standardised residuals answer at O(N M (K + columns)) per product.  One call
+ * = the rows idx[0..b) (idx == NULL: rows 0..b; any order, a duplicate counts as often as it occurs), Q [b, k] (row s belongs to
+ * idx[s], row stride q_stride, a multiple of 4, >= kp, pad cols 0) and ONE head P [M, kp] (kp = nadm_pad_k(k), pad cols 0).  Codes
+ * g in {0, 1, 2} are observed, 3 is missing.  Per call, in fp32:
+ *     pi_ij  = sum_k q_ik p_jk                                      (fused multiply-adds, k in order, as nadm_snp_hwe)
+ *     m_ij   = 1 if the call is observed, j < M and pimin <= pi_ij <= 1 - pimin (1 - pimin rounded to fp32), else 0
+ *     r = clip(pi, eps, 1 - eps);   u = clip(1 - pi, eps, 1 - eps)  (u from the UNCLIPPED pi, as nadm_snp_hwe)
+ *     a_ij   = m_ij (g_ij - 2 pi_ij) / sqrt(2 r u)                  (mean 0 and variance 1 under the model)
+ *     nadm_resid_project     Y[i, c] = sum_j a_ij W[j, c]      ss_i = sum_j a_ij^2      nobs_i = sum_j m_ij
+ *     nadm_resid_project_t   O[j, c] = sum_i a_ij Yin[i, c]                             nobs_snp_j = sum_i m_ij
+ * W float [M, CP], Y float [b, CP], Yin float [b, CP] (row s belongs to idx[s]), O float [M, CP]; ss double [b], nobs int32 [b],
+ * nobs_snp int32 [M].  C in 1..CP columns are in use, CP in {16, 32} is the column stride; pad columns are written as +0.0
+ * (nadm_obs_project's contract: the subspace iteration of neural_admixture_amd/pca.py runs on either pair).  The scale depends on
+ * sample and SNP jointly, so no operand of nadm_obs_project carries it.  k <= 16 (kp in {4, 8, 12, 16}); eps in [1e-9, 0.5), pimin in
+ * [0, 0.5).  scratch: nadm_resid_project_scratch_floats(b, M, CP) / nadm_resid_project_t_scratch_floats(b, M, kp, CP) floats (both
+ * grow with b and with M; 0 for a width without a kernel).  xp, P, Q, W, Yin, Y, O, scratch 16-byte, ss 8-byte, nobs, nobs_snp, idx
+ * 4-byte aligned; ld >= ceil(M/4), ld % 16 == 0, ld < 2^32; the address of row r is r * ld in 64 bits.
+ * Arithmetic: g - 2 pi is ONE fused multiply-add fma(-2, pi, g); the scale is the hardware's 1-ulp reciprocal square root of
+ * (r + r) u; their product is rounded once; every column sum and ss take a by fused multiply-adds on the vector ALU (no matrix pipe,
+ * no operand splitting).  A missing call, a row past the list, a SNP >= M and a masked pi give a = +0.0f exactly: the result does
+ * not depend on the pad bits of a row's last byte nor on the finite values of W at SNPs where a is 0 (rows >= M of P and W are never
+ * read), and an output whose every term is masked is +0.0.  Forward: the 256-SNP chunks are cut into nadm_resid_project_ranges(b, M)
+ * contiguous ranges of nadm_resid_project_chunks(b, M) chunks (the plan of nadm_sample_info); a lane's fp32 column sums cover one
+ * range in SNP order and never more than 2^18 SNPs; ss is an fp32 sum within a chunk and a float64 sum over chunks.  Transposed: the
+ * batch's 64-sample tiles are cut into nadm_resid_project_t_slices(b, M) slices of whole tiles (the rule of nadm_snp_hwe_slices;
+ * never more than 4096 samples in one fp32 sum).  The ranges' / slices' partials are added in float64 in range / slice order and
+ * rounded to fp32 once; the counts are integer sums, exact.  The order depends on (b, M) alone and there are no floating-point
+ * atomics: the same inputs give the same bits.  Every refusal -- a null pointer, an empty block, ld, k and kp, q_stride, eps, pimin,
+ * k > 16, C / CP, alignment -- is reported before anything is launched.  Asynchronous on `stream`. */
+int32_t nadm_resid_project_chunks(int32_t b, int64_t M);
+int32_t nadm_resid_project_ranges(int32_t b, int64_t M);
+int64_t nadm_resid_project_scratch_floats(int32_t b, int64_t M, int32_t CP);
+int nadm_resid_project(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                       const float* P, int32_t k, int32_t kp, const float* Q, int32_t q_stride, float eps, float pimin,
+                       const float* W, int32_t C, int32_t CP, float* Y, double* ss, int32_t* nobs, float* scratch, void* stream);
+int32_t nadm_resid_project_t_slices(int32_t b, int64_t M);
+int64_t nadm_resid_project_t_scratch_floats(int32_t b, int64_t M, int32_t kp, int32_t CP);
+int nadm_resid_project_t(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                         const float* P, int32_t k, int32_t kp, const float* Q, int32_t q_stride, float eps, float pimin,
+                         const float* Yin, int32_t C, int32_t CP, float* O, int32_t* nobs_snp, float* scratch, void* stream);
+
 /* ---- 8(f)-3: decoder init, the means of the mixture the reference fits in the PCA subspace (model/train.py:61-66, scikit-learn's
  * GaussianMixture(n_components=K, n_init=5, init_params='k-means++', tol=1e-4, covariance_type='full', max_iter=100,
  * random_state=seed).fit(X).means_): the EM iterations of that call in float64 on the host (csrc/nadm_gmm.cpp restates the

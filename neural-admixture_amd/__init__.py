@@ -22,9 +22,12 @@ from .pse import p_se, p_info, se_from_info    # noqa: F401  (standard errors of
 from .fitcheck import resid_cor, em_sums, fit_check, group_means, sample_means    # noqa: F401  (model-fit check: correlation of leave-one-out residuals)
 from . import pca                 # noqa: F401  (principal components of the standardised genotypes: pca.pca; the module, whose name its function shares)
 from .pca import obs_project, obs_project_t    # noqa: F401  (its two products: the observed-calls pair products)
+from . import residpca            # noqa: F401  (residual PCA given Q and P: what structure the K components leave, and in which samples)
+from .residpca import resid_pca, resid_project, resid_project_t    # noqa: F401  (its function and its two products of the standardised residuals)
 from . import pack2bit            # noqa: F401  (the reference's native module by its own names: pack2bit.cu:144-147)
 
 __all__ = ["train", "Engine", "ModelLayout", "Q_P", "NeuralAdmixture", "pack2bit", "project_q", "project_p", "polish", "kinship", "kinship_pairs", "king_pairs", "unrelated_set", "select_samples",
            "snp_counts", "ld_band", "prune", "select_snps", "snp_hwe", "snp_hwe_sums", "hwe_keep", "cv_error", "mask_fold", "heldout_deviance",
            "bootstrap_q", "block_weights", "p_se", "p_info", "se_from_info", "q_se", "q_info", "resid_cor", "em_sums", "fit_check", "group_means",
-           "sample_means", "pca", "obs_project", "obs_project_t"]
+           "sample_means", "pca", "obs_project", "obs_project_t", "residpca", "resid_pca", "resid_project",
+           "resid_project_t"]

@@ -141,6 +141,13 @@ def _load():
         "nadm_obs_project_t_slices": (i32, [i32, i64]),
         "nadm_obs_project_t_scratch_floats": (i64, [i32, i64, i32]),
         "nadm_obs_project_t": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, vp, vp, vp, vp]),
+        "nadm_resid_project_chunks": (i32, [i32, i64]),
+        "nadm_resid_project_ranges": (i32, [i32, i64]),
+        "nadm_resid_project_scratch_floats": (i64, [i32, i64, i32]),
+        "nadm_resid_project": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, vp, i32, f32, f32, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "nadm_resid_project_t_slices": (i32, [i32, i64]),
+        "nadm_resid_project_t_scratch_floats": (i64, [i32, i64, i32, i32]),
+        "nadm_resid_project_t": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, vp, i32, f32, f32, vp, i32, i32, vp, vp, vp, vp]),
         "nadm_snp_counts": (C.c_int, [vp, i64, vp, i64, i64, vp, vp]),
         "nadm_ld_band": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp]),
         "nadm_select_snps": (C.c_int, [vp, i64, i64, vp, i64, i32, vp, i64, vp]),

@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|king|kinship|prune|hwe|cv|bootstrap|pse|qse|fit|pca ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|king|kinship|prune|hwe|cv|bootstrap|pse|qse|fit|pca|residpca ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -212,6 +212,28 @@ def parse_pca_args(argv):
     p.add_argument("--maf", type=float, default=0.0,
                    help="leave out the SNPs whose minor-allele frequency is below this (default 0: only unobserved and monomorphic SNPs go)")
     p.add_argument("--seed", type=int, default=42)
+    return p.parse_args(argv)
+
+
+def parse_residpca_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture residpca",
+                                description="Residual PCA: principal components of the standardised residuals given a run's .P and .Q "
+                                            "files, read against the Marchenko-Pastur edge (use LD-pruned data)")
+    _add_run_args(p, multi_k=True, out="eigenvalues and eigenvectors")
+    p.add_argument("--pcs", type=int, default=10, help="principal components to report (default 10)")
+    p.add_argument("--oversample", type=int, default=10,
+                   help="extra columns the subspace iteration carries (default 10); --pcs + --oversample is at most 32")
+    p.add_argument("--iters", type=int, default=10, help="rounds of subspace iteration (default 10)")
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--pimin", type=float, default=0.01,
+                   help="leave out a call whose individual-specific allele frequency is outside [pimin, 1 - pimin] (default 0.01): its "
+                        "standardised residual is heavy-tailed")
+    p.add_argument("--pops_path", type=str, default=None, metavar="FILE",
+                   help="one group label per sample, used only to name the groups at the two ends of a flagged PC (default: every "
+                        "sample goes to its largest component, the groups are named 1..K)")
+    p.add_argument("--warn", type=float, default=1.5,
+                   help="log a warning for every PC whose eigenvalue exceeds this many times the Marchenko-Pastur edge (default 1.5: a "
+                        "convention, not a calibration; LD between SNPs inflates the whole spectrum)")
     return p.parse_args(argv)
 
 
@@ -724,6 +746,46 @@ def _fit_main(argv):
     log.info("    Residual correlations saved.")
 
 
+def _residpca_main(argv):
+    """``residpca`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes -> {out_name}.{K}.resid.eigenval and
+    .resid.eigenvec (the ``pca`` mode's layout), the eigenvalue and its ratio to the Marchenko-Pastur edge per PC in the log, and for
+    every PC above --warn a warning with the groups at its two ends and its five most extreme samples."""
+    from . import residpca
+    from .fitcheck import default_labels
+    args = parse_residpca_args(argv)
+    ks = _ks_asked(args)
+    if max(ks) > residpca.MAX_K:
+        raise SystemExit(f"    residpca needs every K <= 16: {residpca.TOO_WIDE} (K = {max(ks)} was asked for).")
+    try:
+        residpca.check_args(args.pcs, args.oversample, args.iters, args.pimin)
+    except RuntimeError as e:
+        raise SystemExit(f"    {e}") from None
+    if not args.warn >= 0.0:
+        raise SystemExit("    --warn must be >= 0.")
+    labels = None
+    if args.pops_path is not None:
+        if not os.path.isfile(args.pops_path):
+            raise SystemExit(f"    {args.pops_path} not found.")
+        with open(args.pops_path, "r") as fb:
+            labels = [ln.strip() for ln in fb.read().splitlines()]
+        labels = _filter_lines(labels, _sample_keep(args), args.pops_path)
+
+    def check_n(n):
+        if labels is not None and len(labels) != n:
+            raise SystemExit(f"    {args.pops_path} lists {len(labels)} labels, the data holds {n} samples.")
+        if args.pcs > n:
+            raise SystemExit(f"    --pcs {args.pcs} components were asked of {n} samples.")
+    data, Ps, Qs = _read_run_heads(args, ks, "residpca", check_n)
+    log.info("    Residual PCA given Q and P: standardised residuals, calls with a frequency outside "
+             f"[{args.pimin:g}, {1.0 - args.pimin:g}] left out; groups are " +
+             ("the labels of --pops_path." if labels is not None else "the samples' largest components."))
+    results = [residpca.resid_pca(data.packed, data.M, P, Q, pcs=args.pcs, oversample=args.oversample, iters=args.iters,
+                                  pimin=args.pimin, seed=args.seed) for P, Q in zip(Ps, Qs)]
+    residpca.log_results(results, [labels if labels is not None else default_labels(Q)[0] for Q in Qs], log, args.warn)
+    residpca.write_results(args.save_dir, args.out_name or args.name, results)
+    log.info("    Residual eigenvalues and eigenvectors saved.")
+
+
 def _king_main(argv):
     """``king`` mode: the genotypes alone -> {name}.king (``i j phi n hethet ibs0`` per pair at or above --cutoff, 0-based indices
     among the samples analysed, by i then j) and {name}.king.in / .king.out, the kept and the removed samples of ``king.unrelated_set`` as ``FID IID``
@@ -846,14 +908,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 
 _ANALYSIS_MODES = {"king": _king_main, "kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
-                   "pse": _pse_main, "qse": _qse_main, "fit": _fit_main, "pca": _pca_main}
+                   "pse": _pse_main, "qse": _qse_main, "fit": _fit_main, "pca": _pca_main, "residpca": _residpca_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "qse", "fit", "pca"), \
+    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "qse", "fit", "pca", "residpca"), \
         ('Please provide either the argument "train" or "infer" to choose running mode ("king" finds relatives before a run, "kinship", "prune" and "hwe" check a run\'s assumptions, '
-         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "qse" on Q given P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes).')
+         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "qse" on Q given P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes, "residpca" those of the model\'s residuals).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         _ANALYSIS_MODES[mode](argv[1:])

@@ -692,6 +692,18 @@ class Engine:
         self._analysis("pca", "use pca.pca on one GPU from the genotype file")
         return pca.pca(self.xp, self.M, pcs=pcs, oversample=oversample, iters=iters, maf=maf, seed=seed)
 
+    def resid_pca(self, head: int = 0, pcs: int = 10, oversample: int = 10, iters: int = 10, pimin: float = 0.01, seed: int = 42):
+        """Model fit along the sample axis at any N: the principal components of the standardised residuals of the resident matrix
+        given head ``head``'s P and the encoder's final Q (residpca.resid_pca; include/nadm.h, nadm_resid_project /
+        nadm_resid_project_t): a ``ResidPcaResult`` with ``eigenvalues`` ``[pcs]``, ``eigenvectors`` ``[N, pcs]``, ``M_eff``, ``N_eff``,
+        ``total``, the Marchenko-Pastur ``edge`` and ``ratio = eigenvalues / edge`` (above about 1.5: structure the K components do
+        not describe).  K <= 16.  The engine's parameters and optimiser state are left as they are."""
+        from . import residpca
+        residpca.check_args(pcs, oversample, iters, pimin)
+        self._analysis("resid_pca", "use residpca.resid_pca on one GPU from the written .P and .Q files", head=head,
+                       max_k=(residpca.MAX_K, residpca.TOO_WIDE))
+        return residpca.resid_pca(self.xp, self.M, *self._fitted(head), pcs=pcs, oversample=oversample, iters=iters, pimin=pimin, seed=seed)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()

@@ -140,6 +140,31 @@ def orient(U: np.ndarray) -> np.ndarray:
     return U * np.where(big < 0, -1.0, 1.0)
 
 
+def subspace_pcs(times, t_times, M: int, L: int, CP: int, pcs: int, iters: int, seed: int, dev, m_eff):
+    """The randomised subspace iteration shared by ``pca`` and ``residpca.resid_pca``, on the two operators of a matrix ``A [b, M]``:
+    ``times(W)`` takes float64 ``[M, CP]`` on the device (pad columns 0) to ``A W`` as host float64 ``[b, L]``, ``t_times(Q)`` takes
+    host float64 ``[b, <= L]`` to ``A^T Q`` as float64 ``[M, CP]`` on the device (pad columns 0).  Start ``omega(M, L, seed)``,
+    ``iters`` rounds with numpy's QR in float64 on the host between the products, then a Rayleigh-Ritz step in float64: the Gram
+    matrix of the last product through ``svd.gram64``, divided by ``m_eff`` (a number, or a callable asked once the last product has
+    run).  Returns ``(eigenvalues [pcs] of A A^T / m_eff, descending and >= 0, eigenvectors [b, pcs] oriented)``."""
+    from .svd import gram64
+
+    def orth(Y):
+        return np.linalg.qr(Y, mode="reduced")[0]
+
+    W0 = torch.zeros((M, CP), dtype=torch.float64, device=dev)
+    W0[:, :L] = torch.from_numpy(omega(M, L, seed)).to(dev)
+    Y = times(W0)
+    for _ in range(iters):
+        Y = times(t_times(orth(Y)))
+    Q = orth(Y)                                          # [b, min(b, L)]
+    Bt = t_times(Q)
+    T = gram64(Bt[:, :Q.shape[1]]).cpu().numpy() / (m_eff() if callable(m_eff) else m_eff)
+    lam, Wv = np.linalg.eigh(T)
+    order = np.argsort(lam)[::-1][:pcs]
+    return np.maximum(lam[order], 0.0), orient(Q @ Wv[:, order])
+
+
 def pca(xp: torch.Tensor, M: int, pcs: int = 10, oversample: int = 10, iters: int = 10, maf: float = 0.0, seed: int = 42,
         idx=None) -> PcaResult:
     """The top ``pcs`` principal components of the samples ``idx`` (default: every row) of the packed device matrix ``xp [rows, ld]``:
@@ -152,7 +177,6 @@ def pca(xp: torch.Tensor, M: int, pcs: int = 10, oversample: int = 10, iters: in
     b = _shape(xp, M, idx, "pca")
     if pcs > b:
         raise RuntimeError(f"pca: {pcs} components were asked of {b} samples")
-    from .svd import gram64
     with torch.cuda.device(xp.device):
         c, s, m_eff, total = standardise(snp_counts(xp, M, idx), maf)
         dev, CP = xp.device, pad_columns(L)
@@ -172,21 +196,8 @@ def pca(xp: torch.Tensor, M: int, pcs: int = 10, oversample: int = 10, iters: in
             O1, O2 = obs_project_t(xp, M, torch.from_numpy(Qp).to(dev), L, idx, t_scratch)
             return sd * (O1.to(torch.float64) - cd * O2.to(torch.float64))
 
-        def orth(Y):
-            return np.linalg.qr(Y, mode="reduced")[0]
-
-        W0 = torch.zeros((M, CP), dtype=torch.float64, device=dev)
-        W0[:, :L] = torch.from_numpy(omega(M, L, seed)).to(dev)
-        Y = z_times(W0)
-        for _ in range(iters):
-            Y = z_times(zt_times(orth(Y)))
-        Q = orth(Y)                                          # [b, min(b, L)]
-        Bt = zt_times(Q)
-        T = gram64(Bt[:, :Q.shape[1]]).cpu().numpy() / m_eff
-    lam, Wv = np.linalg.eigh(T)
-    order = np.argsort(lam)[::-1][:pcs]
-    values = np.maximum(lam[order], 0.0)
-    return PcaResult(values, orient(Q @ Wv[:, order]), m_eff, values / total, total)
+        values, vectors = subspace_pcs(z_times, zt_times, M, L, CP, pcs, iters, seed, dev, m_eff)
+    return PcaResult(values, vectors, m_eff, values / total, total)
 
 
 def log_result(res: PcaResult, logger=log) -> None:
