@@ -45,7 +45,7 @@ extern "C" {
 #define NADM_MAX_K 64
 #define NADM_MAX_BUCKETS 8
 #define NADM_MAX_P2_SLICES 8   /* sample slices of pass 2 (nadm_decode_bce_sliced) */
-#define NADM_ABI_VERSION 14  /* 14: nadm_clock_probe; new symbols only, same version: nadm_plan_set_precision / nadm_plan_precision (NADM_PRECISION_*), nadm_class_sums + NADM_LABEL_NONE (labels in [-1, k)), nadm_project_q / nadm_project_scratch_floats (projection: Q refined against a fixed P), nadm_snp_counts / nadm_ld_band / nadm_select_snps / nadm_ld_sweep (LD pruning); 13: pass 3 in sample slices (nadm_encode_bwd_sliced, nadm_encode_slices(_max), nadm_encode_slab_floats, nadm_encode_bwd_chunks, nadm_plan_desc_t.p3_slab / p3_cnt); 12: nadm_test_force_slices / nadm_test_force_generic_mlp exist in the test build only (-DNADM_TEST_HOOKS), nadm_calib_clock / nadm_wall_clock_khz; 11: nadm_gmm_fit_means_dev, nadm_loglik_blocks counts 8 row slices per 1024-SNP block, nadm_decode_bce_sliced / nadm_decode_slices / nadm_decode_slab_floats / nadm_test_force_slices + nadm_plan_desc_t.p2_slab / p2_cnt (pass 2 in sample slices when the SNP chunks alone do not fill the chip); 10: message B of the sample-sharded step in SNP-range buckets (nadm_flat_layout takes n_buckets, nadm_flat_layout_t.bkt_*, nadm_plan_desc_t.n_buckets / p3_whole / comm_a / debug, nadm_encode_fwd_part, nadm_plan_bucket_ms), nadm_comm_t.async_error, nadm_comm_rccl_probe, nadm_comm_rccl with a watchdog (timeout_ms), a failed step poisons its plan; 9: nadm_step / nadm_plan_* / nadm_comm_* / nadm_flat_layout (the step as one call, sharded optimizer), nadm_test_force_generic_mlp; 8: nadm_dz_image(_bytes), nadm_mlp_bwd_image; nadm_encode_bwd, nadm_encode_bwd_step, nadm_pca_project_t take the operand image of dZ / Y; 7: nadm_encode_fwd_step, nadm_sum_rows, dqpart of nadm_mlp_bwd is float* (folded in place); 6: nadm_mlp_fwd_images, nadm_decode_bce_images, nadm_q_image_bytes, nadm_encode_fwd_small; 5: nadm_adam_t.when, nadm_adam2, with_loss bit 1; 4: nadm_decode_bce_step, nadm_encode_bwd_step (nadm_adam_t, nadm_mlp_weights_t), nadm_small_grads; 3: nadm_decode_bce_gather; 2: nadm_mlp_bwd_weights, nadm_supervised_ce, nadm_pca_project(_t), nadm_loglik, nadm_savetxt_f32, nadm_decode_chunk_snps; grad_small of nadm_mlp_bwd may be NULL */
+#define NADM_ABI_VERSION 14  /* 14: nadm_clock_probe; new symbols only, same version: nadm_plan_set_precision / nadm_plan_precision (NADM_PRECISION_*), nadm_class_sums + NADM_LABEL_NONE (labels in [-1, k)), nadm_project_q / nadm_project_scratch_floats (projection: Q refined against a fixed P), nadm_snp_counts / nadm_ld_band / nadm_select_snps / nadm_ld_sweep (LD pruning), nadm_ibd / nadm_ibd_ranges / nadm_ibd_scratch_floats + NADM_IBD_MAX_ROWS (IBD-sharing sums given ancestry); 13: pass 3 in sample slices (nadm_encode_bwd_sliced, nadm_encode_slices(_max), nadm_encode_slab_floats, nadm_encode_bwd_chunks, nadm_plan_desc_t.p3_slab / p3_cnt); 12: nadm_test_force_slices / nadm_test_force_generic_mlp exist in the test build only (-DNADM_TEST_HOOKS), nadm_calib_clock / nadm_wall_clock_khz; 11: nadm_gmm_fit_means_dev, nadm_loglik_blocks counts 8 row slices per 1024-SNP block, nadm_decode_bce_sliced / nadm_decode_slices / nadm_decode_slab_floats / nadm_test_force_slices + nadm_plan_desc_t.p2_slab / p2_cnt (pass 2 in sample slices when the SNP chunks alone do not fill the chip); 10: message B of the sample-sharded step in SNP-range buckets (nadm_flat_layout takes n_buckets, nadm_flat_layout_t.bkt_*, nadm_plan_desc_t.n_buckets / p3_whole / comm_a / debug, nadm_encode_fwd_part, nadm_plan_bucket_ms), nadm_comm_t.async_error, nadm_comm_rccl_probe, nadm_comm_rccl with a watchdog (timeout_ms), a failed step poisons its plan; 9: nadm_step / nadm_plan_* / nadm_comm_* / nadm_flat_layout (the step as one call, sharded optimizer), nadm_test_force_generic_mlp; 8: nadm_dz_image(_bytes), nadm_mlp_bwd_image; nadm_encode_bwd, nadm_encode_bwd_step, nadm_pca_project_t take the operand image of dZ / Y; 7: nadm_encode_fwd_step, nadm_sum_rows, dqpart of nadm_mlp_bwd is float* (folded in place); 6: nadm_mlp_fwd_images, nadm_decode_bce_images, nadm_q_image_bytes, nadm_encode_fwd_small; 5: nadm_adam_t.when, nadm_adam2, with_loss bit 1; 4: nadm_decode_bce_step, nadm_encode_bwd_step (nadm_adam_t, nadm_mlp_weights_t), nadm_small_grads; 3: nadm_decode_bce_gather; 2: nadm_mlp_bwd_weights, nadm_supervised_ce, nadm_pca_project(_t), nadm_loglik, nadm_savetxt_f32, nadm_decode_chunk_snps; grad_small of nadm_mlp_bwd may be NULL */
 
 /* Head table shared by the MLP entry points (mirror of NeuralEncoder/NeuralDecoder's ks list,
  * neural_admixture.py:27-29,66-76). Offsets are element offsets into the `small` flat buffer. */
@@ -637,6 +637,47 @@ int64_t nadm_kinship_scratch_floats(int32_t ba, int32_t bb, int64_t M);
 int nadm_kinship(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
                  const float* P, int32_t k, int32_t kp, const float* QA, const float* QB, int32_t q_stride, float pimin,
                  double* num, double* den, int32_t* nobs, float* scratch, void* stream);
+
+/* ---- IBD-sharing sums given ancestry (PC-Relate, Conomos et al. 2016) of one block of sample pairs -------------------------------
+ * What tells a parent-child pair from full siblings (both phi = 0.25): the probabilities k0, k1, k2 that a pair shares 0, 1 or 2
+ * alleles identical by descent.  The estimators are PC-Relate's (Conomos et al. 2016, eqs. for k2 and k0), with the admixture
+ * model's individual-specific frequencies pi in the place of its PC-predicted ones, as REAP (Thornton et al. 2012) uses them.  The
+ * rows, P, QA / QB, pi and the mask m are those of nadm_kinship, word for word; fA [ba] / fB [bb] are the samples' inbreeding
+ * coefficients (f_a = 2 phi_aa - 1 of nadm_kinship), an INPUT, one float per list position (may be the same pointer, as QA / QB).
+ *     v_ij  = pi (1 - pi)
+ *     gD_ij = pi if g = 0;  0 if g = 1;  1 - pi if g = 2            (dominance coding; E[gD] = v (1 + f))
+ *     e_ij  = m (gD - v (1 + f_i))          vm_ij = m v
+ *     u_ij  = m pi^2                        w_ij  = m (1 - pi)^2
+ *     z0_ij = m [g = 0]                     z2_ij = m [g = 2]
+ *     k2num_ab = sum_j e_a e_b              k2den_ab = sum_j vm_a vm_b
+ *     ibs0_ab  = sum_j (z0_a z2_b + z2_a z0_b)                      (int32, exact)
+ *     exp0_ab  = sum_j (u_a w_b + w_a u_b)                          (the expected share of opposite homozygotes with no allele IBD)
+ * The caller forms, in float64, with phi_ab of nadm_kinship on the same block and pimin:
+ *     k2 = k2num / k2den (none where k2den = 0);  k0 = ibs0 / exp0 if phi >= 2^-2.5 (none where exp0 = 0), else 1 - 4 phi + k2;
+ *     k1 = 1 - k0 - k2.
+ * Expected (k0, k1, k2): unrelated (1, 0, 0), parent-child (0, 1, 0), full sibs (1/4, 1/2, 1/4), duplicate (0, 0, 1), second degree
+ * (1/2, 1/2, 0).  The estimates are unconstrained.  Only these formulas are promised, no other tool's printed digits.
+ * k2num, k2den, exp0 double [ba, bb], ibs0 int32 [ba, bb], row-major, none may be NULL.  K <= 16 (a sample's Q row lives in its
+ * builder thread's registers; a wider head is refused).  pimin in [0, 0.5).  ba, bb in 1..NADM_IBD_MAX_ROWS.  scratch:
+ * nadm_ibd_scratch_floats(ba, bb, M) floats (grows with ba, bb and M).  xp, P, QA, QB, scratch 16-byte, the double outputs 8-byte,
+ * ibs0, fA, fB and the lists 4-byte aligned; ld % 16 == 0, ld < 2^32.
+ * A missing call, a SNP >= M, a row past the list and a masked pi enter every sum as exactly +0.0f WHATEVER f IS (a NaN included):
+ * the terms are cleared with bit masks, never multiplied by 0.  e, vm, u and w are formed in fp32 and carried as two
+ * round-to-nearest bf16 pieces each (value to 2^-17 relative), multiplied on the matrix pipe (v_mfma_f32_16x16x32_bf16) as hi.hi +
+ * hi.lo + lo.hi with fp32 accumulation; z0 and z2 are exact in one piece: 14 instructions per 16 x 16 tile and 32 SNPs.  The 256-SNP
+ * chunks are cut into nadm_ibd_ranges(ba, bb, M) contiguous ranges (the plan of nadm_kinship); one fp32 accumulator never covers more
+ * than 2^18 SNPs, so ibs0 -- a sum of ones below 2^24 -- is exact.  The ranges' partials are added in float64 in range order.  Against
+ * float64: |k2num - k2num64| <= 2^-15 sum_j mag_a mag_b with mag = m (|gD| + v (1 + |f|)) (e is a difference formed in fp32),
+ * |k2den - k2den64| <= 2^-15 k2den64, |exp0 - exp0_64| <= 2^-15 exp0_64.  The order depends on (ba, bb, M, kp) alone and there are no
+ * floating-point atomics: the same inputs give the same bits.  Every refusal is reported before anything is launched.  Asynchronous
+ * on `stream`. */
+#define NADM_IBD_MAX_ROWS 4096
+int32_t nadm_ibd_ranges(int32_t ba, int32_t bb, int64_t M);
+int64_t nadm_ibd_scratch_floats(int32_t ba, int32_t bb, int64_t M);
+int nadm_ibd(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
+             const float* P, int32_t k, int32_t kp, const float* QA, const float* QB, int32_t q_stride,
+             const float* fA, const float* fB, float pimin,
+             double* k2num, double* k2den, int32_t* ibs0, double* exp0, float* scratch, void* stream);
 
 /* ---- KING-robust kinship (Manichaikul et al. 2010) of one block of sample pairs, from the genotypes alone -----------------------
  * The check of the "unrelated samples" assumption BEFORE a fit: it needs no allele frequencies and no model, and it is robust to

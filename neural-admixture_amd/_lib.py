@@ -111,6 +111,9 @@ def _load():
         "nadm_kinship_ranges": (i32, [i32, i32, i64]),
         "nadm_kinship_scratch_floats": (i64, [i32, i32, i64]),
         "nadm_kinship": (C.c_int, [vp, i64, vp, i32, vp, i32, i64, vp, i32, i32, vp, vp, i32, f32, vp, vp, vp, vp, vp]),
+        "nadm_ibd_ranges": (i32, [i32, i32, i64]),
+        "nadm_ibd_scratch_floats": (i64, [i32, i32, i64]),
+        "nadm_ibd": (C.c_int, [vp, i64, vp, i32, vp, i32, i64, vp, i32, i32, vp, vp, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp]),
         "nadm_king_ranges": (i32, [i32, i32, i64]),
         "nadm_king_scratch_ints": (i64, [i32, i32, i64]),
         "nadm_king": (C.c_int, [vp, i64, vp, i32, vp, i32, i64, vp, vp, vp]),

@@ -6,7 +6,7 @@ from typing import Optional
 
 import torch
 
-MAX_ROWS = 4096              # rows per block side at most: NADM_KINSHIP_ / NADM_KING_ / NADM_RESID_COR_MAX_ROWS
+MAX_ROWS = 4096              # rows per block side at most: NADM_KINSHIP_ / NADM_IBD_ / NADM_KING_ / NADM_RESID_COR_MAX_ROWS
 
 
 def block_rows(rows: int) -> int:

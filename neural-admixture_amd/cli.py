@@ -175,6 +175,13 @@ def parse_kinship_args(argv):
                    help="list the pairs with a kinship coefficient of at least this (default 0.0442, the lower edge of third-degree relatives)")
     p.add_argument("--pimin", type=float, default=0.0,
                    help="drop a call whose individual-specific allele frequency is outside [pimin, 1 - pimin] (default 0: every observed call counts)")
+    p.add_argument("--ibd", action="store_true",
+                   help="also estimate the IBD-sharing probabilities k0, k1, k2 of the listed pairs (PC-Relate's estimators on the same "
+                        "frequencies) and write {out_name}.{k}.ibd, 'i j phi n k0 k1 k2 ibs0 relation' per pair: k0 tells a parent-offspring "
+                        "pair (0) from full siblings (1/4), which share phi = 0.25.  K must be <= 16")
+    p.add_argument("--po_k0", type=float, default=0.1,
+                   help="with --ibd: a first-degree pair with k0 below this is labelled parent-offspring, otherwise full siblings (default "
+                        "0.1, a convention between the expected 0 and 0.25, not a calibration); in (0, 0.25)")
     return p.parse_args(argv)
 
 
@@ -823,19 +830,36 @@ def _king_main(argv):
 
 def _kinship_main(argv):
     """``kinship`` mode: {save_dir}/{name}.{k}.P and .Q + the genotypes -> {out_name}.{k}.kin (``i j phi n`` per related pair, 0-based
-    sample indices, by i then j) and {out_name}.{k}.inbreed (one inbreeding coefficient per sample)."""
+    sample indices, by i then j) and {out_name}.{k}.inbreed (one inbreeding coefficient per sample); with --ibd also
+    {out_name}.{k}.ibd (``i j phi n k0 k1 k2 ibs0 relation`` per listed pair) and the number of pairs per relation in the log."""
     from . import relate
     from .io import savetxt
     args = parse_kinship_args(argv)
     _check_k_pimin(args)
     if not args.min_phi == args.min_phi:
         raise SystemExit("    --min_phi must be a number.")
+    if args.ibd and args.k > relate.MAX_K:
+        raise SystemExit(f"    kinship --ibd needs K <= 16: {relate.TOO_WIDE} (K = {args.k} was asked for).")
+    if not 0.0 < args.po_k0 < 0.25:
+        raise SystemExit("    --po_k0 must be in (0, 0.25): between the k0 expected of a parent-offspring pair and of full siblings.")
     data, (P,), (Q,) = _read_run_heads(args, [args.k], "kinship")
-    i, j, phi, n, inb = relate.kinship_pairs(data.packed, data.M, P, Q, args.min_phi, pimin=args.pimin)
+    if args.ibd:
+        i, j, phi, n, inb, k0, k1, k2, ibs0 = relate.ibd_pairs(data.packed, data.M, P, Q, args.min_phi, pimin=args.pimin)
+    else:
+        i, j, phi, n, inb = relate.kinship_pairs(data.packed, data.M, P, Q, args.min_phi, pimin=args.pimin)
     phi_h = phi.cpu().numpy()
     stem = f"{_out_stem(args)}.{args.k}"
     relate.write_pairs(f"{stem}.kin", i.cpu().numpy(), j.cpu().numpy(), phi_h, n.cpu().numpy())
     savetxt(f"{stem}.inbreed", inb.cpu().numpy().reshape(-1, 1))
+    if args.ibd:
+        k0_h = k0.cpu().numpy()
+        labels = relate.relation(phi_h, k0_h, args.po_k0)
+        relate.write_ibd(f"{stem}.ibd", i.cpu().numpy(), j.cpu().numpy(), phi_h, n.cpu().numpy(), k0_h, k1.cpu().numpy(), k2.cpu().numpy(),
+                         ibs0.cpu().numpy(), labels)
+        log.info(f"    IBD-sharing probabilities of the {len(labels)} listed pairs (first-degree pairs with k0 < {args.po_k0:g}: parent-offspring):")
+        for label, count in relate.relation_counts(labels):
+            if label != "unrelated" or count:
+                log.info(f"      {label}: {count}")
     log.info(f"    {len(phi_h)} pairs with a kinship coefficient >= {args.min_phi:.4f} among {data.N} samples:")
     for label, edge, count in relate.band_counts(phi_h):
         log.info(f"      {label} (>= {edge:.4f}): {count}")

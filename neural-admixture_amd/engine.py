@@ -635,6 +635,15 @@ class Engine:
         self._analysis("kinship", "use relate.kinship_pairs on one GPU from the written .P and .Q files", head=head)
         return relate.kinship_pairs(self.xp, self.M, *self._fitted(head), relate.MIN_PHI if min_phi is None else min_phi, pimin=pimin)
 
+    def ibd(self, head: int = 0, min_phi: Optional[float] = None, pimin: float = 0.0):
+        """``kinship`` with the IBD-sharing probabilities of the listed pairs (relate.ibd_pairs; include/nadm.h, nadm_ibd): ``(i, j,
+        phi, n, inbreeding, k0, k1, k2, ibs0)``, the first five exactly what ``kinship`` returns.  k0 tells a parent-child pair (0)
+        from full siblings (1/4) at the same phi.  K <= 16.  The engine's parameters and optimiser state are left as they are."""
+        from . import relate
+        self._analysis("ibd", "use relate.ibd_pairs on one GPU from the written .P and .Q files", head=head,
+                       max_k=(relate.MAX_K, relate.TOO_WIDE))
+        return relate.ibd_pairs(self.xp, self.M, *self._fitted(head), relate.MIN_PHI if min_phi is None else min_phi, pimin=pimin)
+
     def king(self, min_phi: Optional[float] = None, rows: int = 1024):
         """KING-robust kinship of the resident matrix's samples (king.king_pairs; include/nadm.h, nadm_king): ``(i, j, phi, n, hethet,
         ibs0)``, the pairs i < j with phi >= ``min_phi`` (default: the lower edge of second-degree relatives).  It reads the genotypes

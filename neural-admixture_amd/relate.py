@@ -12,6 +12,13 @@ a duplicate or twin, (1 + f) / 2 for a sample with itself (f: its inbreeding coe
 
 ``kinship`` is the dense form, ``kinship_pairs`` lists the related pairs holding one block at a time (any N),
 ``Engine.kinship`` runs the latter on the resident matrix with the engine's own P and the encoder's final Q.
+
+A parent-child pair and a pair of full siblings both have phi = 0.25; what tells them apart are the probabilities k0, k1, k2 that the
+pair shares 0, 1 or 2 alleles identical by descent (parent-child 0, 1, 0; full sibs 1/4, 1/2, 1/4).  ``ibd_pairs`` adds them to the
+listed pairs with PC-Relate's estimators (Conomos et al. 2016) on the same pi: k2 from the dominance-coded genotypes, k0 of a
+first-degree or closer pair from the opposite homozygotes it shows against those expected of a pair with no allele IBD, of a more
+distant pair from 1 - 4 phi + k2.  Every block that holds a listed pair is one ``nadm_ibd`` call (include/nadm.h: four Gram products
+on the matrix pipe, K <= 16).  The estimates are unconstrained: values slightly outside [0, 1] are normal, nothing is clipped.
 """
 from __future__ import annotations
 
@@ -28,6 +35,12 @@ ROWS = 1024                  # rows per block side of the dense and the pair for
 MIN_PHI = 2.0 ** -4.5        # lower edge of third-degree relatives (0.0442)
 # lower edges of the usual degree bands (KING's): duplicate / twin, first, second, third degree
 BANDS = ((2.0 ** -1.5, "duplicate or twin"), (2.0 ** -2.5, "first degree"), (2.0 ** -3.5, "second degree"), (2.0 ** -4.5, "third degree"))
+MAX_K = 16                   # widest head of the IBD sums (nadm_ibd)
+TOO_WIDE = "K must be <= 16 for the IBD-sharing probabilities (a sample's Q row lives in its builder thread's registers beside the operand image)"
+# k0 below this in the first-degree band: parent-offspring, otherwise full siblings.  A convention between the expected 0 and 1/4 (as
+# the --warn of the fit check is), not a calibration
+PO_MAX_K0 = 0.1
+RELATIONS = ("duplicate or twin", "parent-offspring", "full siblings", "second degree", "third degree", "unrelated")
 
 
 def kinship_scratch(ba: int, bb: int, M: int, device) -> torch.Tensor:
@@ -128,3 +141,113 @@ def write_pairs(path, i, j, phi, n, *more) -> None:
     with open(path, "w") as fb:
         for a, b, p, *cs in zip(np.asarray(i).tolist(), np.asarray(j).tolist(), np.asarray(phi, dtype=np.float64).tolist(), *ints):
             fb.write(f"{a:d} {b:d} {p:.17g} " + " ".join(f"{c:d}" for c in cs) + "\n")
+
+
+# ------------------------------------------------------------------------------------------------ IBD-sharing probabilities
+def ibd_scratch(ba: int, bb: int, M: int, device) -> torch.Tensor:
+    n = int(lib.nadm_ibd_scratch_floats(ba, bb, M))
+    if n <= 0:
+        raise RuntimeError(f"ibd: a block of {ba} x {bb} rows over {M} SNPs is not supported (1..4096 rows a side)")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def ibd_block(xp: torch.Tensor, M: int, Pp: torch.Tensor, k: int, idxA: Optional[torch.Tensor], QA: torch.Tensor, fA: torch.Tensor,
+              idxB: Optional[torch.Tensor], QB: torch.Tensor, fB: torch.Tensor, pimin: float = 0.0,
+              scratch: Optional[torch.Tensor] = None):
+    """One ``nadm_ibd`` call on the current stream: the operands of ``kinship_block`` and the inbreeding coefficients ``fA [ba]`` /
+    ``fB [bb]`` (float32, row s belongs to ``idx[s]``).  Returns ``(k2num, k2den, exp0)`` float64 and ``ibs0`` int32, each
+    ``[ba, bb]``: ``ibd_of`` turns them into k0, k1, k2.  K <= 16."""
+    ba, bb = int(QA.shape[0]), int(QB.shape[0])
+    check_packed(xp, idxA, ba)
+    check_packed(xp, idxB, bb)
+    for t in (Pp, QA, QB):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.device != xp.device or t.stride(1) != 1:
+            raise RuntimeError("ibd_block: P and Q must be float32 matrices on the packed matrix's device")
+    if not Pp.is_contiguous() or Pp.shape[0] != M:
+        raise RuntimeError(f"ibd_block: P must be a contiguous [{M}, kp] matrix")
+    if Pp.shape[1] > MAX_K:
+        raise RuntimeError(f"ibd_block: {TOO_WIDE}")
+    if QA.stride(0) != QB.stride(0):
+        raise RuntimeError("ibd_block: QA and QB must have the same row stride")
+    for f, b in ((fA, ba), (fB, bb)):
+        if f.dtype != torch.float32 or f.dim() != 1 or f.device != xp.device or not f.is_contiguous() or f.numel() != b:
+            raise RuntimeError("ibd_block: fA and fB must be contiguous float32 vectors of ba and bb entries on the packed matrix's device")
+    dev = xp.device
+    if scratch is None:
+        scratch = ibd_scratch(ba, bb, M, dev)
+    k2num, k2den, exp0 = (torch.empty((ba, bb), dtype=torch.float64, device=dev) for _ in range(3))
+    ibs0 = torch.empty((ba, bb), dtype=torch.int32, device=dev)
+    check(lib.nadm_ibd(ptr(xp), xp.shape[1], ptr(idxA), ba, ptr(idxB), bb, M, ptr(Pp), k, Pp.shape[1], ptr(QA), ptr(QB), QA.stride(0),
+                       ptr(fA), ptr(fB), pimin, ptr(k2num), ptr(k2den), ptr(ibs0), ptr(exp0), ptr(scratch), stream()), "ibd")
+    return k2num, k2den, exp0, ibs0
+
+
+def ibd_of(phi: torch.Tensor, k2num: torch.Tensor, k2den: torch.Tensor, ibs0: torch.Tensor, exp0: torch.Tensor):
+    """``(k0, k1, k2)`` float64 from the four sums and the pairs' kinship coefficient: k2 = k2num / k2den (NaN where k2den == 0);
+    k0 = ibs0 / exp0 where phi >= 2^-2.5, the first-degree edge of ``BANDS`` (NaN where exp0 == 0), else 1 - 4 phi + k2;
+    k1 = 1 - k0 - k2.  Unconstrained: nothing is clipped or renormalised."""
+    phi, k2num, k2den, exp0 = (t.to(torch.float64) for t in (phi, k2num, k2den, exp0))
+    nan = torch.full_like(k2num, float("nan"))
+    k2 = torch.where(k2den != 0, k2num / k2den, nan)
+    k0 = torch.where(phi >= BANDS[1][0], torch.where(exp0 != 0, ibs0.to(torch.float64) / exp0, nan), 1.0 - 4.0 * phi + k2)
+    return k0, 1.0 - k0 - k2, k2
+
+
+def ibd_pairs(xp: torch.Tensor, M: int, P, Q, min_phi: float = MIN_PHI, rows: int = ROWS, pimin: float = 0.0,
+              idx: Optional[torch.Tensor] = None):
+    """The related pairs with their IBD-sharing probabilities: ``(i, j, phi, n, inbreeding, k0, k1, k2, ibs0)``.  The first five are
+    ``kinship_pairs``' own, bit for bit (it runs first and yields every sample's f = 2 phi_aa - 1; a sample without an observed call
+    has none and enters with f = 0: every one of its calls is masked); then the blocks are walked again, a block that holds no listed
+    pair is skipped, every other one is one ``nadm_ibd`` call, and the four sums are gathered at the listed pairs.  ``k0, k1, k2``
+    float64 and ``ibs0`` int32, one per listed pair.  K <= 16."""
+    if np.ndim(P) == 2 and int(np.shape(P)[1]) > MAX_K:
+        raise RuntimeError(f"ibd_pairs: {TOO_WIDE}")
+    i, j, phi, n, inb = kinship_pairs(xp, M, P, Q, min_phi, rows, pimin, idx)
+    dev = xp.device
+    f = torch.where(torch.isnan(inb), torch.zeros_like(inb), inb).to(torch.float32)
+    rows, blocks = walk(n_rows(xp, idx), rows, idx, dev)
+    _, K, Pp, Qp = model_operands(xp, M, idx, P, Q)
+    sums = [torch.zeros(i.numel(), dtype=torch.float64, device=dev) for _ in range(3)]
+    ibs0 = torch.zeros(i.numel(), dtype=torch.int32, device=dev)
+    ia_blk, jb_blk = torch.div(i, rows, rounding_mode="floor"), torch.div(j, rows, rounding_mode="floor")
+    listed = set(zip(ia_blk.tolist(), jb_blk.tolist()))       # the blocks that hold a listed pair (i < j: a <= b)
+    scratch = ibd_scratch(rows, rows, M, dev) if listed else None
+    for a, ba, ia, b, bb, ib in blocks:
+        if (a // rows, b // rows) not in listed:
+            continue
+        got = ibd_block(xp, M, Pp, K, ia, Qp[a:a + ba], f[a:a + ba], ib, Qp[b:b + bb], f[b:b + bb], pimin, scratch)
+        at = torch.nonzero((ia_blk == a // rows) & (jb_blk == b // rows), as_tuple=True)[0]
+        ii, jj = i[at] - a, j[at] - b
+        for out, blk in zip(sums + [ibs0], got):
+            out[at] = blk[ii, jj]
+    k2num, k2den, exp0 = sums
+    return (i, j, phi, n, inb) + ibd_of(phi, k2num, k2den, ibs0, exp0) + (ibs0,)
+
+
+def relation(phi, k0, po_k0: float = PO_MAX_K0) -> list:
+    """A label per pair from its kinship coefficient and k0: the bands of ``BANDS``, the first-degree one split into
+    "parent-offspring" (k0 < ``po_k0``) and "full siblings" (the rest, a NaN k0 included); "unrelated" below the last band.
+    The default ``PO_MAX_K0`` = 0.1 is a convention between the expected 0 and 1/4, not a calibration."""
+    out = []
+    for p, z in zip(np.asarray(phi, dtype=np.float64).reshape(-1).tolist(), np.asarray(k0, dtype=np.float64).reshape(-1).tolist()):
+        label = next((name for edge, name in BANDS if p >= edge), "unrelated")
+        if label == "first degree":
+            label = "parent-offspring" if z < po_k0 else "full siblings"
+        out.append(label)
+    return out
+
+
+def relation_counts(labels) -> list:
+    """``[(label, count)]`` over ``RELATIONS``, in their order."""
+    labels = list(labels)
+    return [(name, labels.count(name)) for name in RELATIONS]
+
+
+def write_ibd(path, i, j, phi, n, k0, k1, k2, ibs0, labels) -> None:
+    """One line ``i j phi n k0 k1 k2 ibs0 relation`` per listed pair: integers as integers, floats with the 17 digits that read back
+    to the same float64, the label with its spaces replaced by ``_``."""
+    cols = [np.asarray(v).tolist() for v in (i, j)] + [np.asarray(phi, dtype=np.float64).tolist(), np.asarray(n).tolist()]
+    cols += [np.asarray(v, dtype=np.float64).tolist() for v in (k0, k1, k2)] + [np.asarray(ibs0).tolist(), list(labels)]
+    with open(path, "w") as fb:
+        for a, b, p, c, z0, z1, z2, s0, lab in zip(*cols):
+            fb.write(f"{a:d} {b:d} {p:.17g} {c:d} {z0:.17g} {z1:.17g} {z2:.17g} {s0:d} {lab.replace(' ', '_')}\n")
