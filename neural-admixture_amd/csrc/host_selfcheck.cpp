@@ -356,8 +356,27 @@ static void check_refusals() {
     REFUSED(nadm_decode_bce(X, ld, I, 16, 4 * ld, Fp, 8, Fp, 8, Fp, Fp, Fp, 1, nullptr), "4 GiB");
 }
 
+// the pair analyses' block rule: the predicate and the refusal agree, and the messages are the entries' own, byte for byte
+static void check_pair_block_rule() {
+    using namespace nadm;
+    const int R = NADM_KINSHIP_MAX_ROWS;
+    CHECK(check_pair_block("nadm_kinship", 1, R, 1, PAIR_MAX_ROWS(NADM_KINSHIP_MAX_ROWS)) == 0 && pair_block_ok(1, R, 1, R));
+    const int64_t empty[4][3] = {{0, 1, 1}, {1, 0, 1}, {1, 1, 0}, {-1, R + 1, 5}};        // (empty comes before too large)
+    for (const auto& s : empty) {
+        CHECK(!pair_block_ok((int)s[0], (int)s[1], s[2], R));
+        CHECK(check_pair_block("nadm_ibd", (int)s[0], (int)s[1], s[2], PAIR_MAX_ROWS(NADM_IBD_MAX_ROWS)) == 1);
+        CHECK(!strcmp(nadm_last_error(), "nadm_ibd: empty block (need ba > 0, bb > 0 and M > 0)"));
+    }
+    for (int side = 0; side < 2; ++side) {
+        CHECK(!pair_block_ok(side ? 1 : R + 1, side ? R + 1 : 1, 9, R));
+        CHECK(check_pair_block("nadm_king", side ? 1 : R + 1, side ? R + 1 : 1, 9, PAIR_MAX_ROWS(NADM_KING_MAX_ROWS)) == 1);
+        CHECK(!strcmp(nadm_last_error(), "nadm_king: ba and bb must be <= NADM_KING_MAX_ROWS"));
+    }
+}
+
 int main() {
     CHECK(nadm_abi_version() == NADM_ABI_VERSION);
+    check_pair_block_rule();
     check_pack(5, 11, 0); check_pack(1, 1, 0); check_pack(0, 7, 0); check_pack(4, 0, 0); check_pack(5, 11, 5);
     check_bed(7, 5, false); check_bed(1, 3, false); check_bed(13, 1030, false); check_bed(7, 5, true); check_bed(13, 1030, true);
     check_vcf();

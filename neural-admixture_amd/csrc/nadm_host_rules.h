@@ -32,6 +32,18 @@ inline int check_eps(const char* who, float eps) {
     return (eps >= 1e-9f && eps < 0.5f) ? 0 : failf(who, "eps must be in [1e-9, 0.5)");
 }
 
+// the block of sample pairs (ba rows x bb rows over M SNPs) of nadm_kinship, nadm_king, nadm_ibd and nadm_resid_cor: the predicate behind
+// their *_ranges / *_scratch_* queries and the refusal of their entries, one rule.  PAIR_MAX_ROWS(NADM_X_MAX_ROWS) passes the bound and
+// the name the message gives it
+#define PAIR_MAX_ROWS(macro) macro, #macro
+inline bool pair_block_ok(int ba, int bb, int64_t M, int max_rows) { return ba > 0 && bb > 0 && ba <= max_rows && bb <= max_rows && M > 0; }
+inline int check_pair_block(const char* who, int ba, int bb, int64_t M, int max_rows, const char* max_name) {
+    if (pair_block_ok(ba, bb, M, max_rows)) return 0;
+    if (ba <= 0 || bb <= 0 || M <= 0) return failf(who, "empty block (need ba > 0, bb > 0 and M > 0)");
+    snprintf(err_buf(), 512, "%s: ba and bb must be <= %s", who, max_name);
+    return 1;
+}
+
 // f(std::integral_constant<int, KP>{}) for kp = KP, one of the eight padded widths of a head (nadm_pad_k)
 template <class F>
 inline int dispatch_kp(const char* who, int kp, F&& f) {

@@ -162,9 +162,7 @@ struct KingSum {
 
 // the launch shape, a rule of (ba, bb, M) alone
 static RangePlan king_plan(int ba, int bb, int64_t M) { return range_plan(M, range_tiles(ba, KING_TILE, bb, KING_TILE), KING_BLOCKS, KING_MAX_CHUNKS); }
-static bool king_shape_ok(int ba, int bb, int64_t M) {
-    return ba > 0 && bb > 0 && ba <= NADM_KING_MAX_ROWS && bb <= NADM_KING_MAX_ROWS && M > 0 && M < (1ll << 31);
-}
+static bool king_shape_ok(int ba, int bb, int64_t M) { return pair_block_ok(ba, bb, M, NADM_KING_MAX_ROWS) && M < (1ll << 31); }
 
 }  // namespace nadm
 
@@ -180,8 +178,7 @@ extern "C" int64_t nadm_king_scratch_ints(int32_t ba, int32_t bb, int64_t M) {
 extern "C" int nadm_king(const uint8_t* xp, int64_t ld, const int32_t* idxA, int32_t ba, const int32_t* idxB, int32_t bb, int64_t M,
                          int32_t* counts, int32_t* scratch, void* stream) {
     if (!xp || !counts || !scratch) return fail("nadm_king: null pointer");
-    if (ba <= 0 || bb <= 0 || M <= 0) return fail("nadm_king: empty block (need ba > 0, bb > 0 and M > 0)");
-    if (ba > NADM_KING_MAX_ROWS || bb > NADM_KING_MAX_ROWS) return fail("nadm_king: ba and bb must be <= NADM_KING_MAX_ROWS");
+    if (check_pair_block("nadm_king", ba, bb, M, PAIR_MAX_ROWS(NADM_KING_MAX_ROWS))) return 1;
     if (M >= (1ll << 31)) return fail("nadm_king: M must be < 2^31 (the counts are int32)");
     if (check_packed("nadm_king", ld, M)) return 1;
     if ((((uintptr_t)xp | (uintptr_t)scratch) & 15) != 0) return fail("nadm_king: xp and scratch must be 16-byte aligned");

@@ -11,12 +11,11 @@
 //                         whose weights are all zero writes +0.0f / 0 partials and returns (wave-uniform).
 //   project_fold_kernel   one wave per sample: adds the partials over the chunks in a fixed order (a, ll in float64) and applies
 //                         q'_k = q_k a_k / (2n), the floor qmin, the renormalisation.
-#include "nadm_common.h"
-#include "nadm_host.h"
+#include "nadm_chunk_ranges.h"
 
 namespace nadm {
 
-constexpr int PROJ_CHUNK = 256;      // SNPs per chunk = 64 bytes of a packed row = four 16-byte loads
+constexpr int PROJ_CHUNK = RANGE_CHUNK;      // SNPs per chunk = 64 bytes of a packed row = four 16-byte loads
 constexpr int PROJ_TILE = 64;        // samples per block (one wave, a lane per sample)
 
 // KP <= 16: the whole chunk of P is staged at once (16 KB at KP = 16); wider heads stage 64 SNPs at a time (16 KB at KP = 64)
@@ -104,12 +103,7 @@ __global__ __launch_bounds__(PROJ_TILE) void project_accum_kernel(
 #pragma unroll 1
         for (int wd = 0; wd < STAGE / 16; ++wd) {               // one 32-bit word = 16 SNPs
             const int wi = st * (STAGE / 16) + wd;
-            uint32_t bits = w[0];
-#pragma unroll
-            for (int t = 1; t < 16; ++t) bits = (wi == t) ? w[t] : bits;     // (w stays in registers: no dynamic index)
-            // SNPs >= M become code 3 here, once per word (wave-uniform), so that the element loop masks on the code alone
-            const int64_t left = M - (j0 + 16 * wi);
-            if (left < 16) bits |= left <= 0 ? 0xFFFFFFFFu : (0xFFFFFFFFu << (2 * (int)left));
+            const uint32_t bits = chunk_word(w, wi, M - (j0 + 16 * wi));     // SNPs >= M as code 3: the element loop masks on the code alone
             float llw = 0.f;
 #pragma unroll 4
             for (int t = 0; t < 16; ++t) {
@@ -117,15 +111,7 @@ __global__ __launch_bounds__(PROJ_TILE) void project_accum_kernel(
                 const uint32_t m = obs_mask(code);
                 const float* pr = Ps + (wd * 16 + t) * KP;
                 float p[KP];
-#pragma unroll
-                for (int k = 0; k < KP; k += 4) {
-                    const float4 t4 = *reinterpret_cast<const float4*>(pr + k);
-                    p[k] = t4.x; p[k + 1] = t4.y; p[k + 2] = t4.z; p[k + 3] = t4.w;
-                }
-                float rr = 0.f;
-#pragma unroll
-                for (int k = 0; k < KP; ++k) rr = fmaf(q[k], p[k], rr);
-                EmTerms e = em_terms(rr, code, m, eps, one_m_eps);
+                EmTerms e = em_terms(dot_row<KP>(q, pr, p), code, m, eps, one_m_eps);
                 uint32_t wj = 1u;
                 float wf = 1.f;
                 if constexpr (WEIGHTED) {                        // every lane reads the same byte: a broadcast

@@ -242,8 +242,7 @@ __global__ __launch_bounds__(256) void resid_cor_fold_kernel(const float* __rest
 // the launch shape, a rule of (ba, bb, M, kp) alone: a "tile" is 256 samples a x one group of b
 static RangePlan rc_plan(int ba, int bb, int64_t M, int kp) { return range_plan(M, range_tiles(ba, RC_ROWS, bb, rc_group(kp)), RC_BLOCKS, RC_MAX_CHUNKS); }
 static bool rc_shape_ok(int ba, int bb, int64_t M, int kp) {
-    return ba > 0 && bb > 0 && ba <= NADM_RESID_COR_MAX_ROWS && bb <= NADM_RESID_COR_MAX_ROWS && M > 0 && kp >= 4 && kp <= RC_MAX_KP &&
-           kp % 4 == 0;
+    return pair_block_ok(ba, bb, M, NADM_RESID_COR_MAX_ROWS) && kp >= 4 && kp <= RC_MAX_KP && kp % 4 == 0;
 }
 
 }  // namespace nadm
@@ -298,9 +297,7 @@ extern "C" int nadm_resid_cor(const uint8_t* xp, int64_t ld, const int32_t* idxA
                               const float* P, int32_t k, int32_t kp, const float* QA, const float* QB, int32_t q_stride, const float* B,
                               const float* C, float eps, double* S, double* Ta, double* Tb, int32_t* nobs, float* scratch, void* stream) {
     if (!xp || !P || !QA || !QB || !B || !C || !S || !Ta || !Tb || !scratch) return fail("nadm_resid_cor: null pointer");
-    if (ba <= 0 || bb <= 0 || M <= 0) return fail("nadm_resid_cor: empty block (need ba > 0, bb > 0 and M > 0)");
-    if (ba > NADM_RESID_COR_MAX_ROWS || bb > NADM_RESID_COR_MAX_ROWS)
-        return fail("nadm_resid_cor: ba and bb must be <= NADM_RESID_COR_MAX_ROWS");
+    if (check_pair_block("nadm_resid_cor", ba, bb, M, PAIR_MAX_ROWS(NADM_RESID_COR_MAX_ROWS))) return 1;
     if (check_packed("nadm_resid_cor", ld, M) || check_head("nadm_resid_cor", k, kp, q_stride) || check_eps("nadm_resid_cor", eps)) return 1;
     if (kp > RC_MAX_KP)
         return fail("nadm_resid_cor: K must be <= 16 (a sample's Q row and the refitted frequencies of a chunk live in registers and LDS)");

@@ -8,13 +8,11 @@
 // The column sums are fp32 multiply-adds on the VALU, a lane per output row (DESIGN.md 4.19 gives the budget and why the matrix pipe was
 // not taken).  Two launches per call and a third for the transposed product's operand image, no floating-point atomics (two launches
 // on the same inputs give the same bits):
-//   resid_project_kernel     a sample-owning kernel on the chunk-range plan of nadm_chunk_ranges.h, laid out as sample_info_accum_kernel:
-//                            one 256-thread block per (tile of 256 rows of the list, range of 256-SNP chunks), a lane per sample.  The
-//                            lane's q row, the chunk's 16 packed words (the next chunk's are loaded under the current chunk's work), the CP
-//                            running sums, ss and n live in registers for the whole range; the chunk's P rows and W rows sit in LDS once
-//                            per block and every lane reads the SAME row (a broadcast).  Per genotype: KP multiply-adds for pi, the mask,
-//                            two clips, one multiply-add for g - 2 pi, one multiply and one reciprocal square root for the scale, CP
-//                            multiply-adds.  ss is an fp32 sum within a chunk and a float64 sum over the range's chunks.
+//   resid_project_kernel     a lane per sample on the chunk-range plan of nadm_chunk_ranges.h: sample_walk's loop written out (that
+//                            header says why) with a second staged matrix.  The CP running sums, ss and n live in registers for the
+//                            whole range; the chunk's P rows and W rows sit in LDS once per block.  Per genotype: KP multiply-adds for
+//                            pi, the mask, two clips, one multiply-add for g - 2 pi, one multiply and one reciprocal square root for
+//                            the scale, CP multiply-adds.  ss is an fp32 sum within a chunk and a float64 sum over the range's chunks.
 //   resid_project_t_kernel   the SNP-owner sweep of nadm_snp_sweep.h over ONE operand image [b][KP + CP] = (q row | Yin row) that
 //                            resid_pack_kernel writes first: the sweep's loader then brings both rows of a sample to LDS as it brings Q
 //                            for the other kernels, unchanged.  A thread's p row, the CP running sums and n live in registers.
@@ -58,11 +56,7 @@ __global__ __launch_bounds__(RP_TILE) void resid_project_kernel(
     const bool wave_live = tile * RP_TILE + (t & ~63) < b;        // wave-uniform
 
     float q[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k += 4) {
-        const float4 t4 = *reinterpret_cast<const float4*>(Q + (int64_t)rr.posc * q_stride + k);
-        q[k] = t4.x; q[k + 1] = t4.y; q[k + 2] = t4.z; q[k + 3] = t4.w;
-    }
+    load_row<KP>(Q + (int64_t)rr.posc * q_stride, q);
     float acc[CP];
 #pragma unroll
     for (int i = 0; i < CP; ++i) acc[i] = 0.f;
@@ -77,18 +71,8 @@ __global__ __launch_bounds__(RP_TILE) void resid_project_kernel(
     for (int64_t c = c_lo; c < c_hi; ++c) {
         const int64_t j0 = c * RANGE_CHUNK;
         if (c > c_lo) __syncthreads();                            // the previous chunk's rows have been read
-        {
-            // the chunk's P and W rows into LDS (rows >= M as zeros: never read from memory), float4 by float4, coalesced
-            const float4* ps = reinterpret_cast<const float4*>(P + j0 * KP);
-            const float4* ws = reinterpret_cast<const float4*>(W + j0 * CP);
-            const int64_t left = M - j0;                          // rows of the chunk that exist
-#pragma unroll
-            for (int e = t; e < RANGE_CHUNK * KP / 4; e += RP_TILE)
-                reinterpret_cast<float4*>(Ps)[e] = e < left * (KP / 4) ? ps[e] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int e = t; e < RANGE_CHUNK * CP / 4; e += RP_TILE)
-                reinterpret_cast<float4*>(Ws)[e] = e < left * (CP / 4) ? ws[e] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        stage_rows<RANGE_CHUNK, KP, RP_TILE>(P, j0, M, Ps);       // the chunk's P and W rows, zeros past M
+        stage_rows<RANGE_CHUNK, CP, RP_TILE>(W, j0, M, Ws);
         uint32_t w[16];
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
@@ -105,25 +89,12 @@ __global__ __launch_bounds__(RP_TILE) void resid_project_kernel(
         float ssc = 0.f;                                          // the chunk's sum of squares: 256 terms in fp32
 #pragma unroll 1
         for (int wi = 0; wi < 16; ++wi) {                         // one 32-bit word = 16 SNPs
-            uint32_t bits = w[0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) bits = (wi == i) ? w[i] : bits;     // (w stays in registers: no dynamic index)
-            // SNPs >= M become code 3 here, once per word (wave-uniform): with them the pad bits of the row's last byte and what lies behind
-            const int64_t left = M - (j0 + 16 * wi);
-            if (left < 16) bits |= left <= 0 ? 0xFFFFFFFFu : (0xFFFFFFFFu << (2 * (int)left));
+            const uint32_t bits = chunk_word(w, wi, M - (j0 + 16 * wi));      // SNPs >= M as code 3
 #pragma unroll 4
             for (int e = 0; e < 16; ++e) {
                 const uint32_t code = (bits >> (2 * e)) & 3u;
                 uint32_t m = obs_mask(code);
-                const float* pr = Ps + (wi * 16 + e) * KP;
-                float pi = 0.f;
-#pragma unroll
-                for (int k = 0; k < KP; k += 4) {                 // a broadcast: the row is read once, four columns at a time
-                    const float4 t4 = *reinterpret_cast<const float4*>(pr + k);
-                    pi = fmaf(q[k], t4.x, pi); pi = fmaf(q[k + 1], t4.y, pi);
-                    pi = fmaf(q[k + 2], t4.z, pi); pi = fmaf(q[k + 3], t4.w, pi);
-                }
-                const float a = resid_term(pi, code, m, eps, one_m_eps, pimin, one_m_pimin);
+                const float a = resid_term(dot_row<KP>(q, Ps + (wi * 16 + e) * KP), code, m, eps, one_m_eps, pimin, one_m_pimin);
                 n += (int)(m & 1u);
                 ssc = fmaf(a, a, ssc);
                 const float* wr = Ws + (wi * 16 + e) * CP;

@@ -3,16 +3,12 @@
 // N M K^2 / 2 work over the packed matrix with the K (K + 1) / 2 running sums per sample, not per SNP.
 //
 // Two launches per call, no floating-point atomics (two launches on the same inputs give the same bits):
-//   sample_info_accum_kernel  a sample-owning kernel on the chunk-range plan of nadm_chunk_ranges.h: one 256-thread block per (tile of 256
-//                             rows of the list, range of consecutive 256-SNP chunks), a lane per sample.  The lane's q row, the chunk's
-//                             16 packed words (the next chunk's are loaded under the current chunk's work), the T = KP (KP + 1) / 2
-//                             running sums of the upper triangle (fp32) and n (int32) live in registers for the whole range.  The chunk's
-//                             P rows sit in LDS once per block and every lane reads the SAME row (a broadcast: project_accum_kernel's
-//                             arrangement).  Per genotype: KP multiply-adds for pi, two clips, one multiply and one reciprocal for the
-//                             weight 1 / (r u), KP multiplies for w p_a, T multiply-adds.  Missing calls (code 3), rows past the list and
-//                             SNPs >= M are code 3 before the decode and enter every sum as exactly +0.0f / 0.  A wave whose 64 rows are
-//                             all past the list stages and waits with the block and skips the arithmetic.  Writes the range's slab
-//                             plane by plane (a wave's stores are contiguous), n as plane T.
+//   sample_info_accum_kernel  the lane-per-sample walk of nadm_chunk_ranges.h (sample_walk: the packed words, the staged P rows, the
+//                             barriers, code 3 for whatever adds nothing) with the T = KP (KP + 1) / 2 running sums of the upper
+//                             triangle (fp32) and n (int32) in registers for the whole range.  Per genotype: KP multiply-adds for pi,
+//                             two clips, one multiply and one reciprocal for the weight 1 / (r u), KP multiplies for w p_a, T
+//                             multiply-adds; code 3 enters every sum as exactly +0.0f / 0.  Writes the range's slab plane by plane (a
+//                             wave's stores are contiguous), n as plane T.
 //   sample_info_fold_kernel   one thread per sample: adds the ranges' partials in range order in float64, applies the factor 2 of the
 //                             binomial(2, pi) call once (exact) and writes the pairs a <= b < K of the REAL columns, a-major.
 // The float64 inverse under the constraint sum_k q_k = 1 is the caller's (neural_admixture_amd/qse.py: nadm_snp_info_se on the
@@ -38,88 +34,34 @@ __global__ __launch_bounds__(SI_TILE) void sample_info_accum_kernel(
     __shared__ __attribute__((aligned(16))) float Ps[RANGE_CHUNK * KP];      // the chunk's P rows (16 KB at KP = 16)
     const int t = threadIdx.x;
     const int range = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - range * tiles;       // tile fastest: neighbours share a chunk of P
-    const auto [c_lo, c_hi] = chunk_range(range, chunks_per_range, chunks);
     const RangeRow rr = range_row(xp, ld, idx, tile * SI_TILE + t, b);
-    const uint32_t inval = ~rr.valid;                             // a row past the list: every call missing
     const bool wave_live = tile * SI_TILE + (t & ~63) < b;        // wave-uniform
 
     float q[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k += 4) {
-        const float4 t4 = *reinterpret_cast<const float4*>(Q + (int64_t)rr.posc * q_stride + k);
-        q[k] = t4.x; q[k + 1] = t4.y; q[k + 2] = t4.z; q[k + 3] = t4.w;
-    }
+    load_row<KP>(Q + (int64_t)rr.posc * q_stride, q);
     float acc[T];
 #pragma unroll
     for (int i = 0; i < T; ++i) acc[i] = 0.f;
     int n = 0;
 
-    u32x4_t nxt[4];
+    sample_walk<KP, SI_TILE>(rr, wave_live, chunk_range(range, chunks_per_range, chunks), ld, M, P, Ps, [&](const uint32_t code, const int s) {
+        const uint32_t m = obs_mask(code);
+        float p[KP];
+        const float pi = dot_row<KP>(q, Ps + s * KP, p);
+        // 1 - pi from the UNCLIPPED product, as em_terms (nadm_common.h)
+        const float r = fminf(fmaxf(pi, eps), one_m_eps);
+        const float u = fminf(fmaxf(1.f - pi, eps), one_m_eps);
+        // the expected information of pi in one call is 2 / (r u); the 2 is the fold's.  Masked: exactly +0.0f
+        const float wt = keepf(__builtin_amdgcn_rcpf(r * u), m);
+        n += (int)(m & 1u);
+        int i = 0;
 #pragma unroll
-    for (int v = 0; v < 4; ++v) nxt[v] = range_piece(rr.x, c_lo, v, ld);
-
-#pragma unroll 1
-    for (int64_t c = c_lo; c < c_hi; ++c) {
-        const int64_t j0 = c * RANGE_CHUNK;
-        if (c > c_lo) __syncthreads();                            // the previous chunk's rows have been read
-        {
-            // the chunk's P rows into LDS (rows >= M as zeros): RANGE_CHUNK * KP / 4 float4, coalesced
-            const float4* src = reinterpret_cast<const float4*>(P + j0 * KP);
-            const int64_t lim = (M - j0) * (KP / 4);              // float4 of the chunk that exist
+        for (int a = 0; a < KP; ++a) {
+            const float wp = wt * p[a];
 #pragma unroll
-            for (int e = t; e < RANGE_CHUNK * KP / 4; e += SI_TILE)
-                reinterpret_cast<float4*>(Ps)[e] = e < lim ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int d = a; d < KP; ++d, ++i) acc[i] = fmaf(wp, p[d], acc[i]);
         }
-        uint32_t w[16];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            w[4 * v] = nxt[v][0] | inval; w[4 * v + 1] = nxt[v][1] | inval;
-            w[4 * v + 2] = nxt[v][2] | inval; w[4 * v + 3] = nxt[v][3] | inval;
-        }
-        {
-            const int64_t cn = min(c + 1, c_hi - 1);              // the next chunk's words, in flight under this chunk's arithmetic
-#pragma unroll
-            for (int v = 0; v < 4; ++v) nxt[v] = range_piece(rr.x, cn, v, ld);
-        }
-        __syncthreads();
-        if (!wave_live) continue;
-#pragma unroll 1
-        for (int wi = 0; wi < 16; ++wi) {                         // one 32-bit word = 16 SNPs
-            uint32_t bits = w[0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) bits = (wi == i) ? w[i] : bits;     // (w stays in registers: no dynamic index)
-            // SNPs >= M become code 3 here, once per word (wave-uniform): with them the pad bits of the row's last byte and what lies behind
-            const int64_t left = M - (j0 + 16 * wi);
-            if (left < 16) bits |= left <= 0 ? 0xFFFFFFFFu : (0xFFFFFFFFu << (2 * (int)left));
-#pragma unroll 4
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t m = obs_mask((bits >> (2 * e)) & 3u);
-                const float* pr = Ps + (wi * 16 + e) * KP;
-                float p[KP];
-                float pi = 0.f;
-#pragma unroll
-                for (int k = 0; k < KP; k += 4) {                 // a broadcast: the row is read once, four columns at a time
-                    const float4 t4 = *reinterpret_cast<const float4*>(pr + k);
-                    p[k] = t4.x; p[k + 1] = t4.y; p[k + 2] = t4.z; p[k + 3] = t4.w;
-                    pi = fmaf(q[k], t4.x, pi); pi = fmaf(q[k + 1], t4.y, pi);
-                    pi = fmaf(q[k + 2], t4.z, pi); pi = fmaf(q[k + 3], t4.w, pi);
-                }
-                // 1 - pi from the UNCLIPPED product, as em_terms (nadm_common.h)
-                const float r = fminf(fmaxf(pi, eps), one_m_eps);
-                const float u = fminf(fmaxf(1.f - pi, eps), one_m_eps);
-                // the expected information of pi in one call is 2 / (r u); the 2 is the fold's.  Masked: exactly +0.0f
-                const float wt = keepf(__builtin_amdgcn_rcpf(r * u), m);
-                n += (int)(m & 1u);
-                int i = 0;
-#pragma unroll
-                for (int a = 0; a < KP; ++a) {
-                    const float wp = wt * p[a];
-#pragma unroll
-                    for (int d = a; d < KP; ++d, ++i) acc[i] = fmaf(wp, p[d], acc[i]);
-                }
-            }
-        }
-    }
+    });
     // the block's slab [T + 1][256]: every lane writes (a lane past the list wrote zeros; the fold never reads it)
     float* out = part + ((int64_t)range * tiles + tile) * ((T + 1) * SI_TILE) + t;
 #pragma unroll
