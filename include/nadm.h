@@ -329,6 +329,16 @@ int nadm_mlp_bwd_image(const nadm_heads_t* hd, const float* small, float* dqpart
                        const float* losspart, int64_t n_loss, double* loss_acc, void* dzimg, int32_t* dz_counters, void* stream);
 #define NADM_X_CLEAN 1     /* flags: xp is nadm_decode_bce_gather's copy of the batch (tiled, rows in batch order, missing calls already 0) */
 int64_t nadm_batch_copy_bytes(int32_t b, int64_t M);
+/* The WHOLE matrix as a tiled, cleaned copy, made once when the matrix is handed over (the rows never change during training): the
+ * layout of the batch copy with b := rows -- byte column c of row r at  (c / 128) * rows * 128 + r * 128 + c % 128  -- every missing
+ * call (code 3) 0, every code of an SNP >= M 0, the last tile 128 bytes wide: nadm_tiled_bytes(rows, M) = ceil(M / 512) * rows * 128
+ * bytes (0 for an empty shape).  A plan that is given the copy (nadm_plan_set_tiles) gathers the batch's rows for its matrix-core
+ * passes out of it: a block's pieces then lie inside one rows x 128 B window instead of one row length apart, and nothing is cleaned
+ * or masked per batch.  Results are bit-identical to the row-major source.  xp [rows, ld] as everywhere (ld % 16 == 0, ld >= ceil(M/4),
+ * ld < 2^32), rows < 2^31, xp and xt 16-byte aligned and not overlapping.  Refusals in this order: null pointer, empty matrix, ld,
+ * rows, alignment, overlap. */
+int64_t nadm_tiled_bytes(int64_t rows, int64_t M);
+int nadm_tile_packed(const uint8_t* xp, int64_t ld, int64_t rows, int64_t M, uint8_t* xt, void* stream);
 int nadm_encode_bwd(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                     const float* dZ, const void* dzimg, int32_t CP, float* dV, int32_t flags, void* stream);
 
@@ -436,7 +446,7 @@ typedef struct nadm_plan_desc {
     float *zsum, *dqsum;                  /* SNP mode: [bmax*CP], [bmax*SP]                                                     */
     void* qimg; int64_t qimg_head_bytes;  /* nadm_mlp_fwd_images (zero-filled once)                                            */
     void* dzimg; int32_t* dzcnt;          /* nadm_mlp_bwd_image  (C <= 8; counters zero-filled once)                            */
-    uint8_t* xg;                          /* nadm_batch_copy_bytes(bmax, M) (C <= 8)                                            */
+    uint8_t* xg;                          /* nadm_batch_copy_bytes(bmax, M) (C <= 8; NULL: pass 3 reads nadm_plan_set_tiles' copy)   */
     double* loss_acc;                     /* [2]: running sum, last step                                                        */
     const nadm_comm_t* comm;              /* NULL: one rank.  Must outlive the plan                                             */
     const nadm_comm_t* comm_a;            /* DP mode: a second communicator for message A (NULL: `comm` carries both)           */
@@ -458,6 +468,11 @@ typedef struct nadm_plan nadm_plan_t;
 int  nadm_plan_create(const nadm_plan_desc_t* desc, nadm_plan_t** out);
 void nadm_plan_destroy(nadm_plan_t* plan);
 int  nadm_plan_set_rows(nadm_plan_t* plan, const uint8_t* xp);
+/* The tiled, cleaned copy of the SAME rows (nadm_tile_packed over the plan's M; caller-owned, must outlive its use): from the next
+ * nadm_step / nadm_plan_infer on, pass 1 (C <= 8) and pass 2 (padded K <= 16 with Q images) gather from it; pass3_too != 0: pass 3
+ * (C <= 8) as well, and pass 2 then writes no batch copy (desc.xg may be NULL for such a plan).  Every other kernel, and every entry
+ * point outside the plan, keeps reading xp.  xt == NULL: back to the row-major matrix; nadm_plan_set_rows forgets the copy too. */
+int  nadm_plan_set_tiles(nadm_plan_t* plan, const uint8_t* xt, int64_t rows, int32_t pass3_too);
 /* supervised mode (neural_admixture.py:460-474): class per resident row in [-1, n_classes), NADM_LABEL_NONE = no label (the row
  * stays out of the supervised term, nadm_supervised_ce); NULL switches it off */
 int  nadm_plan_set_labels(nadm_plan_t* plan, const int32_t* labels, int32_t n_classes, float weight);

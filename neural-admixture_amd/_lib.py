@@ -187,6 +187,8 @@ def _load():
         "nadm_dz_image_bytes": (C.c_int64, [i32]),
         "nadm_dz_image_tile_bytes": (C.c_int64, []),
         "nadm_batch_copy_bytes": (C.c_int64, [i32, i64]),
+        "nadm_tiled_bytes": (C.c_int64, [i64, i64]),
+        "nadm_tile_packed": (C.c_int, [vp, i64, i64, i64, vp, vp]),
         "nadm_dz_image": (C.c_int, [vp, i32, i32, vp, vp]),
         "nadm_vcf_parse_gt": (C.c_int, [C.c_char_p, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
         "nadm_adam": (C.c_int, [vp, vp, vp, vp, i64, i64, f32, i32, f32, vp]),
@@ -201,6 +203,7 @@ def _load():
         "nadm_plan_create": (C.c_int, [C.POINTER(PlanDesc), C.POINTER(vp)]),
         "nadm_plan_destroy": (None, [vp]),
         "nadm_plan_set_rows": (C.c_int, [vp, vp]),
+        "nadm_plan_set_tiles": (C.c_int, [vp, vp, i64, i32]),
         "nadm_plan_set_labels": (C.c_int, [vp, vp, i32, f32]),
         "nadm_plan_set_state": (C.c_int, [vp, i32, i32]),
         "nadm_plan_step_count": (i32, [vp]),

@@ -119,6 +119,7 @@ int nadm::launch_pass2(const Pass2Launch& a) { rec.p2 = a; ++rec.launches; retur
 int nadm::launch_pass3(const Pass3Launch& a) { rec.p3 = a; ++rec.launches; return 0; }
 int nadm::launch_mlp_fwd(const MlpFwdLaunch& a) { rec.mf = a; ++rec.launches; return 0; }
 int nadm::launch_mlp_bwd(const MlpBwdLaunch& a) { rec.mb = a; ++rec.launches; return 0; }
+int nadm::launch_tile_packed(const uint8_t*, int64_t, int64_t, int64_t, uint8_t*, void*) { ++rec.launches; return 0; }
 int nadm::launch_dz_image(const float*, int32_t, int32_t, void*, void*) { ++rec.launches; return 0; }
 int nadm::device_cu_count() { return g_cus; }
 
@@ -144,7 +145,7 @@ static void check_pass2_forms() {
                 for (int32_t ns : {1, 2})
                     for (int med = 0; med < 2; ++med) {
                         const void* qimg = qi ? Vp : nullptr;
-                        nadm::Pass2Launch a{X, ld, I, b, M, Fp, kp, Fp, 8, Fp, Fp, Fp, wl, X, qimg, ns, ns > 1 ? Fp : nullptr, ns > 1 ? I : nullptr, med != 0, Vp};
+                        nadm::Pass2Launch a{nadm::x_rows(X, ld), I, b, M, Fp, kp, Fp, 8, Fp, Fp, Fp, wl, X, qimg, ns, ns > 1 ? Fp : nullptr, ns > 1 ? I : nullptr, med != 0, Vp};
                         auto call = [&] {                       // the plan's step under "medium", the public sliced form under "highest"
                             if (med) return nadm::pass2_step_args(a, "nadm_step", &ad, false) || nadm::pass2(a) ? 1 : 0;
                             return nadm_decode_bce_sliced(X, ld, I, b, M, Fp, kp, Fp, 8, Fp, Fp, Fp, wl, X, &ad, qimg, ns, a.slab, a.counters, Vp);
@@ -222,7 +223,7 @@ static void check_pass1_forms() {
         if (cp > 8) {
             REFUSED(small(&ad), "only the matrix-core pass (CP <= 8) hosts the side blocks");
             REFUSED(nadm_pca_project(X, ld, I, b, M, Fp, cp, Fp, Vp), "CP <= 8");
-            nadm::Pass1Launch a{X, ld, I, b, M, Fp, cp, Fp, 0, 0u, true, nadm::SmallSide{}, Vp};
+            nadm::Pass1Launch a{nadm::x_rows(X, ld), I, b, M, Fp, cp, Fp, 0, 0u, true, nadm::SmallSide{}, Vp};
             LAUNCHED(nadm::pass1(a));
             CHECK(!rec.p1.medium);                                                                       // the VALU kernel is the same under either precision
             continue;
@@ -233,7 +234,7 @@ static void check_pass1_forms() {
         CHECK(rec.p1.ss.part == Fp && !rec.p1.ss.m && rec.p1.side_blocks == 3);
         LAUNCHED(nadm_pca_project(X, ld, I, b, M, Fp, cp, Fp, Vp));
         CHECK(rec.p1.missing_bf16 == 0x3FC0u && !rec.p1.medium);
-        nadm::Pass1Launch a{X, ld, I, b, M, Fp, cp, Fp, 0, 0u, true, nadm::SmallSide{}, Vp};
+        nadm::Pass1Launch a{nadm::x_rows(X, ld), I, b, M, Fp, cp, Fp, 0, 0u, true, nadm::SmallSide{}, Vp};
         LAUNCHED(nadm::pass1(a));
         CHECK(rec.p1.medium && rec.p1.gy == 2);
     }

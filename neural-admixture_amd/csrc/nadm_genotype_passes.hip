@@ -166,7 +166,10 @@ __device__ __forceinline__ int64_t xcd_chunk(const unsigned bid, const unsigned 
 }
 
 // MED (precision "medium", nadm_plan_set_precision): V enters as hi + mid only -- the [lo | 0] operands and their MFMA are gone
-template <int CP, bool MED = false>
+// TILED: xp is the tiled, cleaned copy of the matrix (nadm_tile_packed; XSource, nadm_pass_args.h) and ld its TILE stride: the lane's 16 bytes
+// of a row sit at tile * ld + row * 128 + offset inside the tile, the 800 rows of a batch within one rows x 128 B window instead of 125 KB
+// apart, and no code 3 is left to clear (missing_bf16 is 0: the host refuses the rest)
+template <int CP, bool MED = false, bool TILED = false>
 __global__ __launch_bounds__(512) void encode_fwd_mfma_kernel(const uint8_t* __restrict__ xp, int64_t ld,
                                                               const int32_t* __restrict__ idx, int b, int64_t M,
                                                               const float* V, float* __restrict__ zpart, int tiles_per_block,
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(512) void encode_fwd_mfma_kernel(const uint8_t* __r
     // A missing call (code 3) is 0 in the model (neural_admixture.py:170) and 1.5 = bf16 0x3FC0 in the init-time PCA
     // projection (train.py:52), selected by the caller.  FP4 (E2M1) reads the nibble 00cc as c/2 -- 0, 0.5, 1, 1.5 -- so
     // the 1.5 case is the conversion's native result and the 0 case clears both bits of every code 3 first.
-    const uint32_t kmiss = missing_bf16 == 0u ? 0x55555555u : 0u;
+    const uint32_t kmiss = TILED ? 0u : (missing_bf16 == 0u ? 0x55555555u : 0u);
     // ---- B operands: V rows of this wave's slice, split hi/mid/lo, for the 8 k-steps ----
     // k-step s, lane (q, j): rows kk = 8q + e  <->  SNP slice0 + 64q + 8s + e ; column j: c = j & 7
     // The wave's [256 x CP] slice of V goes through LDS: CP full 16 B / lane loads per lane (r02 read it element by element --
@@ -279,8 +282,11 @@ __global__ __launch_bounds__(512) void encode_fwd_mfma_kernel(const uint8_t* __r
     };
     // row index and row length as UNSIGNED 32-bit factors: one v_mad_u64_u32 per address (a signed 64 x 64 product is that + two
     // v_mul_lo_u32 + a sign extension, per tile and lane, in the chain in front of the gather's load; the launcher refuses rows of 4 GiB and more)
-    const uint32_t ld32 = (uint32_t)ld;
-    auto load_row = [&](int32_t row) -> uint4 { return *reinterpret_cast<const uint4*>(xp + ((uint64_t)(uint32_t)row * ld32 + (uint64_t)byte_off_c)); };
+    const uint32_t ld32 = TILED ? (uint32_t)XG_TILE_COLS : (uint32_t)ld;
+    // TILED: the tile's offset (64-bit) and the piece's offset inside it, once per thread (a chunk is four tiles: the last chunk's tiles
+    // past M do not exist in the copy, hence the clamp as for the rows)
+    const uint64_t src_off = TILED ? (uint64_t)(byte_off_c / XG_TILE_COLS) * (uint64_t)ld + (uint64_t)(byte_off_c % XG_TILE_COLS) : (uint64_t)byte_off_c;
+    auto load_row = [&](int32_t row) -> uint4 { return *reinterpret_cast<const uint4*>(xp + ((uint64_t)(uint32_t)row * ld32 + src_off)); };
     // EM_D - 1 tiles of loads in flight ahead of the compute (a 16-sample tile is ~0.3 us of work per wave, much less
     // than the latency of the dependent idx -> row loads); the row index of the tile after those is fetched too.
     uint4 st[EM_D];
@@ -311,8 +317,10 @@ __global__ __launch_bounds__(512) void encode_fwd_mfma_kernel(const uint8_t* __r
                     // v_cvt_scalef32_pk_bf16_fp4 turns one byte = two nibbles into a bf16 pair: 8 + 16 VALU instructions
                     // per 16 genotypes, no LDS table.  Element order within a k-step: SNPs 0 2 4 6 1 3 5 7 (B matches).
                     uint32_t r = raw[w];
+                    if constexpr (!TILED) {
                     const uint32_t m3 = r & (r >> 1) & kmiss;                 // low bit of every code that is 3
                     r ^= m3 | (m3 << 1);
+                    }
                     const uint32_t ev = r & 0x33333333u, od = (r >> 2) & 0x33333333u;
 #pragma unroll
                     for (int hf = 0; hf < 2; ++hf) {
@@ -749,7 +757,11 @@ constexpr int BF_TS = NADM_BF_TS;       // samples per LDS tile
 // MED: precision "medium" (nadm_plan_set_precision): P and Q enter R^T as hi + mid (the products with a lo piece are
 // dropped), dR is ONE bf16 piece (round to nearest even), no remainder, no lo half in the transposition buffer.  Q operands from the
 // tile images only (the step's form); the images are the same as for "highest" -- the lo pieces in them meet zeros or no MFMA.
-template <int KP, bool LOSS, bool UNIT_P = true, bool QIMG = false, bool SLICED = false, bool PROBE = false, bool MED = false>
+// CLEAN_SRC: xp is the tiled, cleaned copy of the matrix (nadm_tile_packed; XSource, nadm_pass_args.h) and ld its TILE stride.  A block's 64
+// byte columns are one half of tile chunk / 2: its pieces of the batch's rows lie within one rows x 128 B window, and what the loader did
+// to every loaded word for every batch -- missing calls to 0, the bytes past M to 0 -- was done once when the copy was made; only the rows
+// past b of a ragged last tile (clamped loads of row b - 1) are still masked.  The step's form (Q images); nothing in the tile loop differs.
+template <int KP, bool LOSS, bool UNIT_P = true, bool QIMG = false, bool SLICED = false, bool PROBE = false, bool MED = false, bool CLEAN_SRC = false>
 __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(bf_wpe(KP), bf_wpe(KP)))) void decode_bce_bf16_kernel(
     const uint8_t* __restrict__ xp, int64_t ld, const int32_t* __restrict__ idx, int b, int64_t M,
     float* P, const float* __restrict__ Q, int SP,
@@ -786,7 +798,7 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
     constexpr int KW = W ? 16 : 8;                       // k columns of the operand images
     static_assert(BF_NTW == 4 || BF_NTW == 2, "tile bits are read as one 32- or 16-bit word");
     constexpr int NTW = BF_NTW, MF_WAVES = BF_WAVES, MF_TS = BF_TS;
-    constexpr int RB = MF_WAVES * 4 * NTW;               // 128 packed bytes per row per block
+    constexpr int RB = MF_WAVES * 4 * NTW;               // 64 packed bytes per row per block
     constexpr int RS = RB + MF_RS_PAD;
     constexpr int PPR = RB / 16;
     constexpr int NTHR = 64 * MF_WAVES;
@@ -921,9 +933,11 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
     const bool has_piece = tid < NPIECE, has_q = tid < MF_TS * KW / QPT;
     const int pr = has_piece ? tid / PPR : 0, pc16 = tid % PPR;
     const int64_t poff = byte0 + pc16 * 16;
-    const bool pcol_ok = poff * 4 < M;             // not `< ld`: on an SNP sub-range launch the bytes past M belong to the next range
-    const uint32_t pcol_okm = lt_mask64(poff * 4, M);
-    const int64_t poff_c = pcol_ok ? poff : 0;
+    const bool pcol_ok = CLEAN_SRC || poff * 4 < M;             // not `< ld`: on an SNP sub-range launch the bytes past M belong to the next range
+    const uint32_t pcol_okm = CLEAN_SRC ? ~0u : lt_mask64(poff * 4, M);     // (the copy holds zeros past M, and its last tile is whole)
+    static_assert(XG_TILE_COLS % RB == 0, "a block's byte columns lie inside one tile of the copy");
+    const int64_t poff_c = CLEAN_SRC ? (poff / XG_TILE_COLS) * ld + poff % XG_TILE_COLS : (pcol_ok ? poff : 0);
+    const uint32_t rstride = CLEAN_SRC ? (uint32_t)XG_TILE_COLS : (uint32_t)ld;
     auto row_index = [&](int i0) -> int32_t { const int smp = i0 + pr; return idx[smp < b ? smp : b - 1]; };
     int32_t row_pref = row_index(0);
     uint4 stage;
@@ -949,7 +963,7 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
         }
         // (unsigned 32-bit factors: one v_mad_u64_u32; the signed 64 x 64 product -- two v_mul_lo_u32 and a sign extension more per tile and thread, in the chain
         // in front of the tile's gather load -- cost the launch 1.2 %, more than their 4.6 issue cycles each: profiles/r06_abl_p2addr.txt; the launcher refuses rows of 4 GiB and more)
-        stage = *reinterpret_cast<const uint4*>(xp + ((uint64_t)(uint32_t)row_pref * (uint32_t)ld + (uint64_t)poff_c));
+        stage = *reinterpret_cast<const uint4*>(xp + ((uint64_t)(uint32_t)row_pref * rstride + (uint64_t)poff_c));
         row_pref = row_index(i0 + MF_TS);
     };
     auto commit = [&](int i0) {
@@ -957,7 +971,12 @@ __global__ __launch_bounds__(64 * BF_WAVES) __attribute__((amdgpu_waves_per_eu(b
         const uint32_t okm = pcol_okm & lt_mask(i0 + pr, b);           // (a select here is four 23-cycle v_cndmask per tile, nadm_common.h)
         // missing calls -> 0 HERE, once per loaded word (r03; until then every lane cleaned the word it took out of the tile): the tile
         // and the copy for pass 3 both hold the model's input
-        const uint4 cl = make_uint4(clean_codes(stage.x & okm), clean_codes(stage.y & okm), clean_codes(stage.z & okm), clean_codes(stage.w & okm));
+        uint4 cl;
+        if constexpr (CLEAN_SRC) {
+            cl = stage;
+            if (i0 + MF_TS > b) cl = make_uint4(stage.x & okm, stage.y & okm, stage.z & okm, stage.w & okm);     // block-uniform: the ragged last tile
+        } else
+        cl = make_uint4(clean_codes(stage.x & okm), clean_codes(stage.y & okm), clean_codes(stage.z & okm), clean_codes(stage.w & okm));
         if (has_piece) *reinterpret_cast<uint4*>(&s_x[pr * RS + pc16 * 16]) = cl;
         // by-product for pass 3: the batch as a copy of its own, missing calls already 0, TILED the way pass 3 walks it -- tile t = the
         // 128 byte columns of pass 3's chunk t, [b rows][128 bytes] back to back (xg_piece).  A block of pass 3 then streams ONE
@@ -1318,7 +1337,9 @@ __global__ __launch_bounds__(256) void dz_image_kernel(const float* __restrict__
 
 constexpr int EB4_XS = 132;               // bytes per byte column of the LDS tile: 128 samples + 4 (dword stride 33: the loader's 4-byte
                                           // stores of 32 consecutive column quads and the 4-byte column reads spread over the banks)
-// CLEAN_SRC: xp is pass 2's copy of the batch (xg_piece: tiled by this kernel's chunks, rows in batch order, missing calls already 0)
+// CLEAN_SRC: xp is a tiled, cleaned copy (XSource, nadm_pass_args.h: tiled by this kernel's chunks, missing calls already 0) and ld its TILE
+// stride -- pass 2's copy of the batch (xg_piece, rows in batch order: a stream), or, GATHER, the resident copy of the whole matrix
+// (nadm_tile_packed), whose rows idx selects: 128-byte lines gathered inside one rows x 128 B window
 
 // SLICED (r06): S sample slices.  The grid is one block per 512-SNP chunk with the batch's 128-sample tiles as a loop inside:
 // a rank of the SNP-sharded mode (6400 rows x 62.5k SNPs at configs[3] on 8 GPUs) launches 122 blocks on 256 CUs and runs 75 us where the
@@ -1326,7 +1347,7 @@ constexpr int EB4_XS = 132;               // bytes per byte column of the LDS ti
 // [512 x CP] sum in `slab`, is counted, and the block counted LAST adds the S partials in slice order and runs the epilogue (Adam on the
 // chunk's V rows, or the gradient store) -- pass 2's idiom (decode_bce_bf16_kernel), the hand-off and its contract in nadm_common.h: nobody
 // waits, the sum's order is fixed, S is a function of (b, M) alone (nadm_encode_slices).  false compiles the kernel as it stood.
-template <int CP, bool CLEAN_SRC, bool SLICED = false>
+template <int CP, bool CLEAN_SRC, bool SLICED = false, bool GATHER = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void encode_bwd_fp4_kernel(const uint8_t* __restrict__ xp, int64_t ld,
                                                               const int32_t* __restrict__ idx, int b, int64_t M,
                                                               const uint4* __restrict__ dzimg, float* __restrict__ dV,
@@ -1368,14 +1389,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int t = 0; t < 4; ++t) lmask[t] = lt_mask64((loff + 4 * t) * 4, M);
     auto row_idx = [&](int i0, int k) -> int32_t {
         const int smp = i0 + 4 * rq + k, smc = smp < b ? smp : b - 1;
-        if constexpr (CLEAN_SRC) return smc;                  // the copy holds the batch in order
+        if constexpr (CLEAN_SRC && !GATHER) return smc;       // the copy holds the batch in order
         else return idx[smc];
     };
     int32_t rows[4];
     uint4 xw[4];
     const uint32_t ld32 = (uint32_t)ld;                       // (a row is < 4 GB)
     static_assert(XG_TILE_COLS == EB_COLS, "the batch copy is tiled by this kernel's chunks");
-    const uint8_t* const xtile = xp + chunk * ((int64_t)b * XG_TILE_COLS) + 16 * cgrp;
+    const uint8_t* const xtile = xp + chunk * (CLEAN_SRC ? ld : (int64_t)0) + 16 * cgrp;
     const bool col_edge = (byte0 + EB_COLS) * 4 > M;          // block-uniform: only the last chunk has byte columns past M
     auto fetch_rows = [&](int i0) {
 #pragma unroll
@@ -1384,7 +1405,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     auto issue = [&]() {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            if constexpr (CLEAN_SRC) xw[k] = *reinterpret_cast<const uint4*>(xtile + rows[k] * XG_TILE_COLS);       // one contiguous b x 128 B region per block
+            if constexpr (CLEAN_SRC) xw[k] = *reinterpret_cast<const uint4*>(xtile + (uint64_t)(uint32_t)rows[k] * (uint32_t)XG_TILE_COLS);       // one contiguous rows x 128 B region per block
             else xw[k] = *reinterpret_cast<const uint4*>(xp + ((uint64_t)(uint32_t)rows[k] * ld32 + (uint64_t)loff_c));   // one v_mad_u64_u32
         }
     };
@@ -1582,6 +1603,39 @@ static int launch_gather_rows(const uint8_t* xp, int64_t ld, const int32_t* idx,
     return check_launch("gather_rows");
 }
 
+// The whole matrix as a tiled, cleaned copy (nadm_tile_packed; XSource, nadm_pass_args.h): tile t = the byte columns 128 t .. 128 t + 127 of
+// every row as [rows][128 B], missing calls 0, the bytes past SNP M 0, the last tile whole.  Made once when the matrix is handed over: the
+// passes then find a batch's pieces of a tile inside one rows x 128 B window and have nothing left to clean.  One thread per 16-byte piece
+// of the copy, the rows walked by a grid-stride loop (a row count does not fit a grid dimension other than x).
+__global__ __launch_bounds__(256) void tile_packed_kernel(const uint8_t* __restrict__ xp, int64_t ld, int64_t rows, int64_t M, int64_t tiles,
+                                                          uint8_t* __restrict__ xt) {
+    constexpr int PPT = XG_TILE_COLS / 16;                          // pieces per row and tile
+    const int64_t n = rows * tiles * PPT;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int64_t t = e / (rows * PPT), r = (e / PPT) % rows;
+        const int64_t col = t * XG_TILE_COLS + (e % PPT) * 16;     // consecutive threads: consecutive pieces of the copy, 128 B runs of a row
+        uint4 w = make_uint4(0, 0, 0, 0);
+        if (col * 4 < M) {                                          // (ld is a multiple of 16 and >= ceil(M / 4): the piece lies inside the row)
+            w = *reinterpret_cast<const uint4*>(xp + r * ld + col);
+            auto below_m = [&](int64_t c) -> uint32_t {            // the codes of the dword at byte column c that belong to SNPs < M
+                const int64_t keep = M - c * 4;
+                return keep >= 16 ? ~0u : (keep <= 0 ? 0u : (1u << (2 * (int)keep)) - 1u);
+            };
+            w = make_uint4(clean_codes(w.x) & below_m(col), clean_codes(w.y) & below_m(col + 4), clean_codes(w.z) & below_m(col + 8),
+                           clean_codes(w.w) & below_m(col + 12));
+        }
+        *reinterpret_cast<uint4*>(xt + e * 16) = w;
+    }
+}
+
+int launch_tile_packed(const uint8_t* xp, int64_t ld, int64_t rows, int64_t M, uint8_t* xt, void* stream) {
+    const int64_t tiles = (M + 4 * XG_TILE_COLS - 1) / (4 * XG_TILE_COLS);
+    int64_t gx = (rows * tiles * (XG_TILE_COLS / 16) + 255) / 256;
+    if (gx > 65536) gx = 65536;
+    hipLaunchKernelGGL(tile_packed_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, xp, ld, rows, M, tiles, xt);
+    return check_launch("tile_packed");
+}
+
 // measurement only: where pass 2's probe block leaves its two counter differences (NULL: no probe).  Process-wide, like the launches' device.
 static std::atomic<unsigned long long*> g_clock_probe{nullptr};
 extern "C" void nadm_clock_probe(uint64_t* out2_dev) { g_clock_probe.store(reinterpret_cast<unsigned long long*>(out2_dev)); }
@@ -1600,13 +1654,15 @@ static int launch_decode_mfma(const Pass2Launch& a, hipStream_t st) {
     unsigned long long* const clk_probe = (a.sliced || a.medium) ? nullptr : g_clock_probe.load();
     dispatch_int<0, 1, 3>(a.loss ? (a.unit_p ? 1 : 3) : 0, [&](auto wl) {          // 3: the loss value with P possibly outside [0, 1]
         constexpr bool LOSS = decltype(wl)::value != 0, UNIT_P = decltype(wl)::value != 3;
-        dispatch_bool([&](auto qi, auto sl, auto pr, auto md) {
+        dispatch_bool([&](auto qi, auto sl, auto pr, auto md, auto cs) {
             constexpr bool QIMG = decltype(qi)::value, SLICED = decltype(sl)::value, PROBE = decltype(pr)::value, MED = decltype(md)::value;
-            if constexpr (!(PROBE && (SLICED || MED)) && !(MED && !QIMG))
-                hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, LOSS, UNIT_P, QIMG, SLICED, PROBE, MED>), grid, block, 0, st, a.xp, a.ld, a.idx, a.b, a.M,
+            constexpr bool CLEAN_SRC = decltype(cs)::value;
+            if constexpr (!(PROBE && (SLICED || MED)) && !(MED && !QIMG) && !(CLEAN_SRC && !QIMG))
+                hipLaunchKernelGGL((decode_bce_bf16_kernel<KP, LOSS, UNIT_P, QIMG, SLICED, PROBE, MED, CLEAN_SRC>), grid, block, 0, st, a.x.base,
+                                   CLEAN_SRC ? a.x.tile_stride : a.x.row_stride, a.idx, a.b, a.M,
                                    a.P, a.Q, a.SP, a.dP, a.dqpart, a.losspart, a.xg, a.ad, static_cast<const uint4*>(a.qimg), a.slab, a.counters,
                                    clk_probe);
-        }, CAN_IMG && a.qimg != nullptr, a.sliced, clk_probe != nullptr, a.medium);
+        }, CAN_IMG && a.qimg != nullptr, a.sliced, clk_probe != nullptr, a.medium, a.x.clean);
     });
     return check_launch(a.medium ? "decode_bce_bf16 (medium)" : "decode_bce_bf16");
 }
@@ -1617,11 +1673,11 @@ static int launch_decode(const Pass2Launch& a, hipStream_t st) {
     const int64_t chunks = (a.M + 256 * SPL - 1) / (256 * SPL);
     dim3 grid((unsigned)chunks), block(256);
     dispatch_bool([&](auto loss) {
-        hipLaunchKernelGGL((decode_bce_kernel<KP, SPL, decltype(loss)::value>), grid, block, 0, st, a.xp, a.ld, a.idx, a.b, a.M, a.P, a.Q, a.SP, a.dP,
+        hipLaunchKernelGGL((decode_bce_kernel<KP, SPL, decltype(loss)::value>), grid, block, 0, st, a.x.base, a.x.row_stride, a.idx, a.b, a.M, a.P, a.Q, a.SP, a.dP,
                            a.dqpart, a.losspart);
     }, a.loss);
     if (check_launch("decode_bce")) return 1;
-    if (a.xg && launch_gather_rows(a.xp, a.ld, a.idx, a.b, a.M, a.xg, st)) return 1;
+    if (a.xg && launch_gather_rows(a.x.base, a.x.row_stride, a.idx, a.b, a.M, a.xg, st)) return 1;
     return a.ad.m ? launch_adam_range(a.P, a.dP, a.ad, a.M * KP, st, 1) : 0;
 }
 
@@ -1659,10 +1715,11 @@ int launch_pass1(const Pass1Launch& a) {
     hipStream_t st = (hipStream_t)a.stream;
     if (a.CP <= 8) {                                    // the matrix-core kernel: 1-D grid of chunks x batch splits, side blocks last
         dim3 grid((unsigned)(a.chunks * a.gy + a.side_blocks)), block(512);
-        dispatch_bool([&](auto c4, auto med) {
-            hipLaunchKernelGGL((encode_fwd_mfma_kernel<decltype(c4)::value ? 4 : 8, decltype(med)::value>), grid, block, 0, st, a.xp, a.ld, a.idx, a.b,
-                               a.M, a.V, a.zpart, a.tpb, a.missing_bf16, (int)a.chunks, a.gy, a.ss);
-        }, a.CP == 4, a.medium);
+        dispatch_bool([&](auto c4, auto med, auto tiled) {
+            constexpr bool TILED = decltype(tiled)::value;
+            hipLaunchKernelGGL((encode_fwd_mfma_kernel<decltype(c4)::value ? 4 : 8, decltype(med)::value, TILED>), grid, block, 0, st, a.x.base,
+                               TILED ? a.x.tile_stride : a.x.row_stride, a.idx, a.b, a.M, a.V, a.zpart, a.tpb, a.missing_bf16, (int)a.chunks, a.gy, a.ss);
+        }, a.CP == 4, a.medium, a.x.clean);
         return check_launch("encode_fwd_mfma");
     }
     const int rpb = enc_rows_per_block(a.b);
@@ -1672,7 +1729,7 @@ int launch_pass1(const Pass1Launch& a) {
     dispatch_int<12, 16, 24, 32>(a.CP, [&](auto cp) {
         constexpr int CP = decltype(cp)::value;
         if (lds > 48 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_fwd_kernel<CP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) hipLaunchKernelGGL((encode_fwd_kernel<CP>), grid, block, lds, st, a.xp, a.ld, a.idx, a.b, a.M, a.V, a.zpart, rpb);
+        if (e == hipSuccess) hipLaunchKernelGGL((encode_fwd_kernel<CP>), grid, block, lds, st, a.x.base, a.x.row_stride, a.idx, a.b, a.M, a.V, a.zpart, rpb);
     });
     if (e != hipSuccess) {
         snprintf(err_buf(), 512, "nadm_encode_fwd: cannot raise dynamic LDS limit to %zu: %s", lds, hipGetErrorString(e));
@@ -1699,15 +1756,17 @@ int launch_pass3(const Pass3Launch& a) {
             extra = (int64_t)side.gx * nadm_sample_splits(a.b);
         }
         dim3 grid((unsigned)(((a.M + EB_CHUNK_SNPS - 1) / EB_CHUNK_SNPS) * a.n_slices + extra)), block(256);
-        dispatch_bool([&](auto c4, auto clean, auto sliced) {
-            hipLaunchKernelGGL((encode_bwd_fp4_kernel<decltype(c4)::value ? 4 : 8, decltype(clean)::value, decltype(sliced)::value>), grid, block, 0, st,
-                               a.xp, a.ld, a.idx, a.b, a.M, (const uint4*)a.dzimg, a.dV, a.missing_bf16, a.V, a.ad, side, a.slab, a.counters, (int)a.n_slices);
-        }, a.CP == 4, a.clean, a.sliced);
+        dispatch_bool([&](auto c4, auto clean, auto sliced, auto gather) {
+            constexpr bool CLEAN = decltype(clean)::value, GATHER = decltype(gather)::value;
+            if constexpr (CLEAN || !GATHER)
+            hipLaunchKernelGGL((encode_bwd_fp4_kernel<decltype(c4)::value ? 4 : 8, CLEAN, decltype(sliced)::value, GATHER>), grid, block, 0, st,
+                               a.x.base, CLEAN ? a.x.tile_stride : a.x.row_stride, a.idx, a.b, a.M, (const uint4*)a.dzimg, a.dV, a.missing_bf16, a.V, a.ad, side, a.slab, a.counters, (int)a.n_slices);
+        }, a.CP == 4, a.clean, a.sliced, a.clean && a.gather);
         return check_launch("encode_bwd_fp4");
     }
     dim3 grid((unsigned)((a.M + 1023) / 1024)), block(256);
     dispatch_int<12, 16, 24, 32>(a.CP, [&](auto cp) {
-        hipLaunchKernelGGL((encode_bwd_kernel<decltype(cp)::value>), grid, block, 0, st, a.xp, a.ld, a.idx, a.b, a.M, a.dZ, a.dV);
+        hipLaunchKernelGGL((encode_bwd_kernel<decltype(cp)::value>), grid, block, 0, st, a.x.base, a.x.row_stride, a.idx, a.b, a.M, a.dZ, a.dV);
     });
     if (check_launch("encode_bwd")) return 1;
     if (a.ad.m && launch_adam_range(a.V, a.dV, a.ad, a.M * a.CP, st, 0)) return 1;  // fp32 variants of pass 3: stand-alone update

@@ -130,6 +130,7 @@ int launch_pass2(const Pass2Launch& a);
 int launch_pass3(const Pass3Launch& a);
 int launch_mlp_fwd(const MlpFwdLaunch& a);
 int launch_mlp_bwd(const MlpBwdLaunch& a);
+int launch_tile_packed(const uint8_t* xp, int64_t ld, int64_t rows, int64_t M, uint8_t* xt, void* stream);
 int launch_dz_image(const float* dZ, int32_t b, int32_t CP, void* dzimg, void* stream);
 int device_cu_count();              // compute units of the current device (256 if the runtime cannot say)
 

@@ -37,6 +37,20 @@ constexpr int dec_spl(int kp) { return kp <= 8 ? 8 : (kp <= 16 ? 4 : (kp <= 32 ?
 // the batch copy pass 2 leaves for pass 3 (nadm_decode_bce_gather): byte `col` of batch row `row` lives in tile col / 128 of
 // [b rows][128 bytes]
 constexpr int XG_TILE_COLS = 128;
+// Where a pass reads X.  Byte column c of row r lives at  base + (c / 128) * tile_stride + r * row_stride + c % 128:
+//   the caller's row-major matrix   row_stride = ld,  tile_stride = 128,        raw codes (a missing call is code 3)
+//   a tiled copy of `rows` rows     row_stride = 128, tile_stride = rows * 128, clean: missing calls and the bytes past SNP M are 0, the last
+//                                   tile is 128 bytes wide (nadm_tile_packed: the whole matrix, rows = N; pass 2's batch copy: rows = b)
+// An SNP sub-range launch advances `base` by whole tiles (x_from_snp); on a tiled source it ends on a tile boundary or at the matrix's end.
+struct XSource {
+    const uint8_t* base;
+    int64_t row_stride, tile_stride;
+    bool clean;
+};
+constexpr XSource x_rows(const uint8_t* xp, int64_t ld) { return XSource{xp, ld, XG_TILE_COLS, false}; }
+constexpr XSource x_tiled(const uint8_t* xt, int64_t rows) { return XSource{xt, XG_TILE_COLS, rows * XG_TILE_COLS, true}; }
+// the same source from SNP m0 on (m0 a multiple of 512: a whole number of tiles)
+constexpr XSource x_from_snp(XSource x, int64_t m0) { return XSource{x.base + (m0 / (4 * XG_TILE_COLS)) * x.tile_stride, x.row_stride, x.tile_stride, x.clean}; }
 // Q as the operand images of the bf16 pass 2 (layout: nadm_common.h)
 constexpr int QI_TS = 64;                                  // samples per tile (= NADM_BF_TS of the pass-2 build)
 constexpr int QI_TILE_U4 = 768;                            // uint4 per tile image in global memory (K <= 8 uses the first 640)
@@ -84,7 +98,7 @@ struct SmallSide {
 // ---- one struct per launch.  The first block of each is what the caller passed; "decided" is what the checked path of the host unit
 // (pass1 .. mlp_bwd) adds before it calls the launcher.  The launchers check nothing.
 struct Pass1Launch {
-    const uint8_t* xp; int64_t ld; const int32_t* idx; int32_t b; int64_t M;
+    XSource x; const int32_t* idx; int32_t b; int64_t M;
     const float* V; int32_t CP; float* zpart;
     int64_t total_chunks;           // > 0: the launch is one part of a pass of that many chunks (nadm_encode_fwd_part)
     uint32_t missing_bf16;          // a missing call as a bf16 pattern: 0, or 0x3FC0 = 1.5 (nadm_pca_project)
@@ -98,7 +112,7 @@ struct Pass1Launch {
 };
 
 struct Pass2Launch {
-    const uint8_t* xp; int64_t ld; const int32_t* idx; int32_t b; int64_t M;
+    XSource x; const int32_t* idx; int32_t b; int64_t M;
     float* P; int32_t kp; const float* Q; int32_t SP; float* dP; float* dqpart; float* losspart;
     int32_t with_loss;              // the caller's bit set
     uint8_t* xg; const void* qimg;
@@ -112,7 +126,7 @@ struct Pass2Launch {
 };
 
 struct Pass3Launch {
-    const uint8_t* xp; int64_t ld; const int32_t* idx; int32_t b; int64_t M;
+    XSource x; const int32_t* idx; int32_t b; int64_t M;
     const float* dZ; const void* dzimg; int32_t CP; float* V; float* dV;
     const nadm_mlp_weights_t* weights;      // the MLP weight-gradient partials as side work, or NULL
     int32_t flags; uint32_t missing_bf16;
@@ -120,7 +134,8 @@ struct Pass3Launch {
     void* stream;
     // decided
     AdamFused ad;
-    bool clean;                     // xp is pass 2's batch copy (NADM_X_CLEAN) and a missing call is 0
+    bool clean;                     // x is a tiled clean copy and a missing call is 0: the loader neither cleans nor, past the edges, masks columns
+    bool gather;                    // clean: the copy's rows are the matrix's (idx selects them); false: pass 2's batch copy, rows in batch order
     bool sliced;                    // n_slices > 1
 };
 

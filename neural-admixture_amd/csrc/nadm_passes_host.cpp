@@ -28,8 +28,33 @@ extern "C" int64_t nadm_encode_bwd_chunks(int64_t M) { return (M + EB_CHUNK_SNPS
 
 extern "C" int64_t nadm_q_image_bytes(int32_t b) { return (int64_t)((b + QI_TS - 1) / QI_TS) * QI_TILE_U4 * 16; }
 extern "C" int64_t nadm_batch_copy_bytes(int32_t b, int64_t M) { return ((M + 4 * XG_TILE_COLS - 1) / (4 * XG_TILE_COLS)) * (int64_t)b * XG_TILE_COLS; }
+extern "C" int64_t nadm_tiled_bytes(int64_t rows, int64_t M) {
+    return rows > 0 && M > 0 ? ((M + 4 * XG_TILE_COLS - 1) / (4 * XG_TILE_COLS)) * rows * XG_TILE_COLS : 0;
+}
 extern "C" int64_t nadm_dz_image_tile_bytes(void) { return (int64_t)DZI_TILE_U4 * 16; }
 extern "C" int64_t nadm_dz_image_bytes(int32_t b) { return (int64_t)((b + DZI_TS - 1) / DZI_TS) * DZI_TILE_U4 * 16; }
+
+// =================================================================================================
+// the tiled, cleaned copy of the matrix and the X source of a pass (XSource, nadm_pass_args.h)
+// =================================================================================================
+extern "C" int nadm_tile_packed(const uint8_t* xp, int64_t ld, int64_t rows, int64_t M, uint8_t* xt, void* stream) {
+    if (!xp || !xt) return fail("nadm_tile_packed: null pointer");
+    if (rows <= 0 || M <= 0) return fail("nadm_tile_packed: empty matrix");
+    if (check_packed("nadm_tile_packed", ld, M)) return 1;
+    if (rows >> 31) return fail("nadm_tile_packed: at most 2^31 - 1 rows (the passes' row indices are int32)");
+    if (((uintptr_t)xp | (uintptr_t)xt) & 15) return fail("nadm_tile_packed: xp and xt must be 16-byte aligned");
+    const uint8_t* xe = xp + rows * ld; const uint8_t* te = xt + nadm_tiled_bytes(rows, M);
+    if (xp < te && xt < xe) return fail("nadm_tile_packed: xt overlaps xp");
+    return launch_tile_packed(xp, ld, rows, M, xt, stream);
+}
+
+// a tiled source as the step hands it over (the public forms of the passes only build row-major ones): refused in the pass's name
+static int tiled_source_args(const char* who, const XSource& x) {
+    if (x.row_stride != XG_TILE_COLS || x.tile_stride < XG_TILE_COLS || x.tile_stride % XG_TILE_COLS != 0)
+        return failf(who, "a tiled source has rows of 128 bytes and tiles of rows x 128 bytes");
+    if ((uintptr_t)x.base & 15) return failf(who, "a tiled source must be 16-byte aligned");
+    return 0;
+}
 
 // =================================================================================================
 // sample slices, the host's side of slice_tiles (nadm_pass_args.h), shared by passes 2 and 3
@@ -172,10 +197,16 @@ int nadm::pass1_small_args(Pass1Launch& a, const float* small_part, int32_t spli
 }
 
 int nadm::pass1(Pass1Launch a) {
-    if (!a.xp || !a.idx || !a.V || !a.zpart) return fail("nadm_encode_fwd: null pointer");
+    if (!a.x.base || !a.idx || !a.V || !a.zpart) return fail("nadm_encode_fwd: null pointer");
     if (a.b <= 0 || a.M <= 0) return fail("nadm_encode_fwd: empty batch or M");
-    if (a.ld % 16 != 0 || a.ld * 4 < a.M) return fail("nadm_encode_fwd: ld must be a multiple of 16 and >= ceil(M/4)");
-    if (a.ld >> 32) return fail("nadm_encode_fwd: rows of 4 GiB and more (ld >= 2^32) are not supported");      // the matrix pass forms row addresses from 32-bit factors
+    if (a.x.clean) {
+        if (tiled_source_args("nadm_encode_fwd", a.x)) return 1;
+        if (a.missing_bf16 != 0u) return fail("nadm_encode_fwd: a missing call read as 1.5 needs the row-major matrix (the tiled copy holds no code 3)");
+        if (a.CP > 8) return fail("nadm_encode_fwd: the tiled copy feeds the matrix-core pass only (C <= 8)");
+    } else {
+    if (a.x.row_stride % 16 != 0 || a.x.row_stride * 4 < a.M) return fail("nadm_encode_fwd: ld must be a multiple of 16 and >= ceil(M/4)");
+    if (a.x.row_stride >> 32) return fail("nadm_encode_fwd: rows of 4 GiB and more (ld >= 2^32) are not supported");      // the matrix pass forms row addresses from 32-bit factors
+    }
     a.chunks = nadm_encode_chunks(a.M);
     if (a.CP <= 8) {
         a.gy = pass1_batch_splits(a.b, a.chunks, a.total_chunks, device_cu_count(), &a.tpb);
@@ -190,18 +221,18 @@ int nadm::pass1(Pass1Launch a) {
 
 extern "C" int nadm_encode_fwd(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                const float* V, int32_t CP, float* zpart, void* stream) {
-    return pass1(Pass1Launch{xp, ld, idx, b, M, V, CP, zpart, 0, 0u, false, SmallSide{}, stream});
+    return pass1(Pass1Launch{x_rows(xp, ld), idx, b, M, V, CP, zpart, 0, 0u, false, SmallSide{}, stream});
 }
 
 extern "C" int nadm_encode_fwd_part(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                     const float* V, int32_t CP, float* zpart, int64_t total_chunks, void* stream) {
-    return pass1(Pass1Launch{xp, ld, idx, b, M, V, CP, zpart, total_chunks, 0u, false, SmallSide{}, stream});
+    return pass1(Pass1Launch{x_rows(xp, ld), idx, b, M, V, CP, zpart, total_chunks, 0u, false, SmallSide{}, stream});
 }
 
 extern "C" int nadm_encode_fwd_small(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                      const float* V, int32_t CP, float* zpart, const float* small_part, int32_t splits, int32_t n_small,
                                      float* grad_small, float* small, const nadm_adam_t* adam, void* stream) {
-    Pass1Launch a{xp, ld, idx, b, M, V, CP, zpart, 0, 0u, false, SmallSide{}, stream};
+    Pass1Launch a{x_rows(xp, ld), idx, b, M, V, CP, zpart, 0, 0u, false, SmallSide{}, stream};
     if (pass1_small_args(a, small_part, splits, n_small, grad_small, small, adam)) return 1;
     return pass1(a);
 }
@@ -209,7 +240,7 @@ extern "C" int nadm_encode_fwd_small(const uint8_t* xp, int64_t ld, const int32_
 extern "C" int nadm_pca_project(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                 const float* V, int32_t CP, float* zpart, void* stream) {
     if (CP > 8) return fail("nadm_pca_project: only the matrix-core pass (CP <= 8) has the missing = 1.5 variant");
-    return pass1(Pass1Launch{xp, ld, idx, b, M, V, CP, zpart, 0, 0x3FC0u, false, SmallSide{}, stream});
+    return pass1(Pass1Launch{x_rows(xp, ld), idx, b, M, V, CP, zpart, 0, 0x3FC0u, false, SmallSide{}, stream});
 }
 
 // =================================================================================================
@@ -222,10 +253,13 @@ int nadm::pass2_step_args(Pass2Launch& a, const char* who, const nadm_adam_t* ad
 }
 
 int nadm::pass2(Pass2Launch a) {
-    if (!a.xp || !a.idx || !a.P || !a.Q || !a.dP || !a.dqpart) return fail("nadm_decode_bce: null pointer");
+    if (!a.x.base || !a.idx || !a.P || !a.Q || !a.dP || !a.dqpart) return fail("nadm_decode_bce: null pointer");
     if (a.medium && a.kp <= 16 && (!a.qimg || NADM_BF_TS != QI_TS))        // (kp > 16: the VALU kernel, the same under either precision)
         return fail("nadm_step: precision \"medium\" runs pass 2 from the Q images (nadm_plan_desc_t.qimg) at padded K <= 16");
-    if (a.ld >> 32) return fail("nadm_decode_bce: rows of 4 GiB and more (ld >= 2^32) are not supported");      // the matrix pass forms row addresses from 32-bit factors
+    if (a.x.clean) {
+        if (tiled_source_args("nadm_decode_bce", a.x)) return 1;
+        if (a.kp > 16 || !a.qimg) return fail("nadm_decode_bce: the tiled copy feeds the matrix-core pass from the Q images only (padded K <= 16, qimg)");
+    } else if (a.x.row_stride >> 32) return fail("nadm_decode_bce: rows of 4 GiB and more (ld >= 2^32) are not supported");      // the matrix pass forms row addresses from 32-bit factors
     if (slice_args(a.n_slices, (a.b + NADM_BF_TS - 1) / NADM_BF_TS, a.slab, a.counters, "nadm_decode_bce_sliced: n_slices must be in 1..8",
                    a.kp > 16 ? "nadm_decode_bce_sliced: sample slices exist for padded K <= 16 only" : nullptr,
                    "nadm_decode_bce_sliced: n_slices > 1 needs the slab (16-byte aligned) and the counters",
@@ -237,7 +271,7 @@ int nadm::pass2(Pass2Launch a) {
     a.unit_p = !(a.loss && (a.with_loss & 2));          // 3: the loss value with P possibly outside [0, 1] (before the first restrict_P)
     if (a.loss && !a.losspart) return fail("nadm_decode_bce: with_loss needs losspart");
     if (a.b <= 0 || a.M <= 0) return fail("nadm_decode_bce: empty batch or M");
-    if (a.ld % 16 != 0 || a.ld * 4 < a.M) return fail("nadm_decode_bce: ld must be a multiple of 16 and >= ceil(M/4)");
+    if (!a.x.clean && (a.x.row_stride % 16 != 0 || a.x.row_stride * 4 < a.M)) return fail("nadm_decode_bce: ld must be a multiple of 16 and >= ceil(M/4)");
     if (dispatch_kp("nadm_decode_bce", a.kp, [](auto) {})) return 1;
     a.sliced = a.n_slices > 1;
     return launch_pass2(a);
@@ -246,20 +280,20 @@ int nadm::pass2(Pass2Launch a) {
 extern "C" int nadm_decode_bce(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                const float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
                                float* losspart, int32_t with_loss, void* stream) {
-    return pass2(Pass2Launch{xp, ld, idx, b, M, const_cast<float*>(P), kp, Q, SP, dP, dqpart, losspart, with_loss, nullptr, nullptr, 1, nullptr, nullptr, false, stream});
+    return pass2(Pass2Launch{x_rows(xp, ld), idx, b, M, const_cast<float*>(P), kp, Q, SP, dP, dqpart, losspart, with_loss, nullptr, nullptr, 1, nullptr, nullptr, false, stream});
 }
 
 extern "C" int nadm_decode_bce_gather(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                       const float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
                                       float* losspart, int32_t with_loss, uint8_t* xg, void* stream) {
     if (!xg) return fail("nadm_decode_bce_gather: null pointer");
-    return pass2(Pass2Launch{xp, ld, idx, b, M, const_cast<float*>(P), kp, Q, SP, dP, dqpart, losspart, with_loss, xg, nullptr, 1, nullptr, nullptr, false, stream});
+    return pass2(Pass2Launch{x_rows(xp, ld), idx, b, M, const_cast<float*>(P), kp, Q, SP, dP, dqpart, losspart, with_loss, xg, nullptr, 1, nullptr, nullptr, false, stream});
 }
 
 extern "C" int nadm_decode_bce_step(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                     float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
                                     float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, void* stream) {
-    Pass2Launch a{xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, nullptr, 1, nullptr, nullptr, false, stream};
+    Pass2Launch a{x_rows(xp, ld), idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, nullptr, 1, nullptr, nullptr, false, stream};
     if (pass2_step_args(a, "nadm_decode_bce_step", adam, true)) return 1;
     return pass2(a);
 }
@@ -268,7 +302,7 @@ extern "C" int nadm_decode_bce_images(const uint8_t* xp, int64_t ld, const int32
                                       float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
                                       float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, const void* qimg,
                                       void* stream) {
-    Pass2Launch a{xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, qimg, 1, nullptr, nullptr, false, stream};
+    Pass2Launch a{x_rows(xp, ld), idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, qimg, 1, nullptr, nullptr, false, stream};
     if (pass2_step_args(a, "nadm_decode_bce_images", adam, false)) return 1;
     if (!qimg) return fail("nadm_decode_bce_images: qimg is NULL (use nadm_decode_bce_step)");
     return pass2(a);
@@ -278,7 +312,7 @@ extern "C" int nadm_decode_bce_sliced(const uint8_t* xp, int64_t ld, const int32
                                       float* P, int32_t kp, const float* Q, int32_t SP, float* dP, float* dqpart,
                                       float* losspart, int32_t with_loss, uint8_t* xg, const nadm_adam_t* adam, const void* qimg,
                                       int32_t n_slices, float* slab, int32_t* counters, void* stream) {
-    Pass2Launch a{xp, ld, idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, qimg, n_slices, slab, counters, false, stream};
+    Pass2Launch a{x_rows(xp, ld), idx, b, M, P, kp, Q, SP, dP, dqpart, losspart, with_loss, xg, qimg, n_slices, slab, counters, false, stream};
     if (pass2_step_args(a, "nadm_decode_bce_sliced", adam, false)) return 1;
     return pass2(a);
 }
@@ -304,17 +338,24 @@ int nadm::pass3_step_args(Pass3Launch& a, const char* who, const nadm_adam_t* ad
 }
 
 int nadm::pass3(Pass3Launch a) {
-    if (!a.xp || !a.idx || !a.dZ || !a.dV) return fail("nadm_encode_bwd: null pointer");
-    if (a.CP > 8 && (a.flags & NADM_X_CLEAN)) return fail("nadm_encode_bwd: the batch copy (NADM_X_CLEAN) is tiled for the matrix-core pass, C <= 8");
+    if (!a.x.base || !a.idx || !a.dZ || !a.dV) return fail("nadm_encode_bwd: null pointer");
+    const bool resident = a.x.clean;                    // the step's tiled copy of the whole matrix; NADM_X_CLEAN: pass 2's copy of the batch, handed over like a matrix
+    if (resident && (a.flags & NADM_X_CLEAN)) return fail("nadm_encode_bwd: NADM_X_CLEAN names pass 2's batch copy, not the tiled copy of the matrix");
+    if (a.CP > 8 && ((a.flags & NADM_X_CLEAN) || resident)) return fail("nadm_encode_bwd: the batch copy (NADM_X_CLEAN) is tiled for the matrix-core pass, C <= 8");
     if (a.CP <= 8 && (!a.dzimg || ((uintptr_t)a.dzimg & 15)))
         return fail("nadm_encode_bwd: C <= 8 runs on the FP4 x FP6 matrix instruction and needs the operand image of dZ (nadm_dz_image), 16-byte aligned");
     if (a.b <= 0 || a.M <= 0) return fail("nadm_encode_bwd: empty batch or M");
-    if (a.ld % 16 != 0 || a.ld * 4 < a.M) return fail("nadm_encode_bwd: ld must be a multiple of 16 and >= ceil(M/4)");
+    if (resident) {
+        if (tiled_source_args("nadm_encode_bwd", a.x)) return 1;
+        if (a.missing_bf16 != 0u) return fail("nadm_encode_bwd: a missing call read as 1.5 needs the row-major matrix (the tiled copy holds no code 3)");
+    } else if (a.x.row_stride % 16 != 0 || a.x.row_stride * 4 < a.M) return fail("nadm_encode_bwd: ld must be a multiple of 16 and >= ceil(M/4)");
     if (a.CP <= 8) {
         if (slice_args(a.n_slices, (a.b + DZI_TS - 1) / DZI_TS, a.slab, a.counters, "nadm_encode_bwd_sliced: n_slices must be in 1..8", nullptr,
                        "nadm_encode_bwd_sliced: the slab (16-byte aligned) and the counters are NULL",
                        "nadm_encode_bwd_sliced: an empty sample slice")) return 1;
-        a.clean = (a.flags & NADM_X_CLEAN) != 0 && a.missing_bf16 == 0u;
+        a.clean = resident || ((a.flags & NADM_X_CLEAN) != 0 && a.missing_bf16 == 0u);
+        a.gather = resident;
+        if (a.clean && !resident) a.x = x_tiled(a.x.base, a.b);
         a.sliced = a.n_slices > 1;
         return launch_pass3(a);
     }
@@ -325,19 +366,19 @@ int nadm::pass3(Pass3Launch a) {
 
 extern "C" int nadm_encode_bwd(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                const float* dZ, const void* dzimg, int32_t CP, float* dV, int32_t flags, void* stream) {
-    return pass3(Pass3Launch{xp, ld, idx, b, M, dZ, dzimg, CP, nullptr, dV, nullptr, flags, 0u, 1, nullptr, nullptr, stream});
+    return pass3(Pass3Launch{x_rows(xp, ld), idx, b, M, dZ, dzimg, CP, nullptr, dV, nullptr, flags, 0u, 1, nullptr, nullptr, stream});
 }
 
 extern "C" int nadm_pca_project_t(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                   const float* Y, const void* yimg, int32_t CP, float* out, void* stream) {
     if (CP > 8) return fail("nadm_pca_project_t: only the matrix-core pass (CP <= 8) has the missing = 1.5 variant");
-    return pass3(Pass3Launch{xp, ld, idx, b, M, Y, yimg, CP, nullptr, out, nullptr, 0, 0x3FC0u, 1, nullptr, nullptr, stream});
+    return pass3(Pass3Launch{x_rows(xp, ld), idx, b, M, Y, yimg, CP, nullptr, out, nullptr, 0, 0x3FC0u, 1, nullptr, nullptr, stream});
 }
 
 extern "C" int nadm_encode_bwd_step(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                     const float* dZ, const void* dzimg, int32_t CP, float* V, float* dV, const nadm_adam_t* adam,
                                     const nadm_mlp_weights_t* weights, int32_t flags, void* stream) {
-    Pass3Launch a{xp, ld, idx, b, M, dZ, dzimg, CP, V, dV, weights, flags, 0u, 1, nullptr, nullptr, stream};
+    Pass3Launch a{x_rows(xp, ld), idx, b, M, dZ, dzimg, CP, V, dV, weights, flags, 0u, 1, nullptr, nullptr, stream};
     if (pass3_step_args(a, "nadm_encode_bwd_step", adam, false)) return 1;
     return pass3(a);
 }
@@ -345,7 +386,7 @@ extern "C" int nadm_encode_bwd_step(const uint8_t* xp, int64_t ld, const int32_t
 extern "C" int nadm_encode_bwd_sliced(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
                                       const float* dZ, const void* dzimg, int32_t CP, float* V, float* dV, const nadm_adam_t* adam,
                                       const nadm_mlp_weights_t* weights, int32_t flags, int32_t n_slices, float* slab, int32_t* counters, void* stream) {
-    Pass3Launch a{xp, ld, idx, b, M, dZ, dzimg, CP, V, dV, weights, flags, 0u, n_slices, slab, counters, stream};
+    Pass3Launch a{x_rows(xp, ld), idx, b, M, dZ, dzimg, CP, V, dV, weights, flags, 0u, n_slices, slab, counters, stream};
     if (pass3_step_args(a, "nadm_encode_bwd_sliced", adam, true)) return 1;
     return pass3(a);
 }

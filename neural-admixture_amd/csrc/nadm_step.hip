@@ -240,6 +240,11 @@ struct nadm_plan {
     int step_count = 0;
     bool p_unit = true;
     bool poisoned = false;                                       // a step failed part-way: see include/nadm.h
+    // the tiled, cleaned copy of the resident rows (nadm_plan_set_tiles; NULL: the passes gather from the row-major matrix) and whether
+    // pass 3 reads it too (then pass 2 writes no batch copy)
+    const uint8_t* xt = nullptr;
+    int64_t xt_rows = 0;
+    bool p3_tiles = false;
     int32_t precision = NADM_PRECISION_HIGHEST;                  // matmul precision of passes 1 and 2 (nadm_plan_set_precision)
     // what the last step left to the next one (see the head of this file)
     bool small_pending = false;
@@ -310,10 +315,15 @@ int flush_small(nadm_plan* p, void* stream) {
     return 0;
 }
 
+// where the matrix-core passes of the step read X: the tiled copy when the plan has one, else the row-major matrix
+XSource x_of(const nadm_plan* p, bool matrix_core) {
+    return p->xt && matrix_core ? x_tiled(p->xt, p->xt_rows) : x_rows(p->d.xp, p->d.ld);
+}
+
 // pass 1 over the whole matrix in the plan's matmul precision, no side blocks
 Pass1Launch pass1_of(const nadm_plan* p, const int32_t* idx, int b, void* stream) {
     const nadm_plan_desc_t& d = p->d;
-    return Pass1Launch{d.xp, d.ld, idx, b, d.M, d.params + p->lay.off_v, d.heads.CP, d.zpart, 0, 0u, p->precision == NADM_PRECISION_MEDIUM, SmallSide{}, stream};
+    return Pass1Launch{x_of(p, d.heads.CP <= 8), idx, b, d.M, d.params + p->lay.off_v, d.heads.CP, d.zpart, 0, 0u, p->precision == NADM_PRECISION_MEDIUM, SmallSide{}, stream};
 }
 
 // DP mode: pass 1 in the parts message B's buckets cut V into.  Part j reads V's range j only, so it waits for bucket j of the
@@ -332,7 +342,7 @@ int encode_fwd_parts(nadm_plan* p, const int32_t* idx, int b, hipStream_t st) {
             if (pass1(pass1_of(p, idx, b, fs))) return 1;
         } else {
             Pass1Launch a = pass1_of(p, idx, b, fs);                 // one part of the pass: the SNP range of bucket j
-            a.xp += m0 / 4; a.M = m1 - m0; a.V += m0 * hd.CP; a.zpart += nadm_encode_chunks(m0) * (int64_t)b * hd.CP; a.total_chunks = p->enc_chunks;
+            a.x = a.x.clean ? x_from_snp(a.x, m0) : x_rows(a.x.base + m0 / 4, a.x.row_stride); a.M = m1 - m0; a.V += m0 * hd.CP; a.zpart += nadm_encode_chunks(m0) * (int64_t)b * hd.CP; a.total_chunks = p->enc_chunks;
             if (pass1(a)) return 1;
         }
         if (j > 0) HIP_OK(hipEventRecord(p->ev_p1[j], fs), "hipEventRecord");
@@ -394,7 +404,8 @@ int decode_heads(nadm_plan* p, const int32_t* idx, int b, int with_loss, const f
         float* slab = d.dqpart + dq_off;
         float* lossp = d.losspart + p->loss_off[h];
         const float* Qh = d.Q + hd.qoff[h];
-        uint8_t* xg = (h == 0 && hd.CP <= 8) ? d.xg : nullptr;          // head 0's launch leaves the batch copy for pass 3
+        const bool p3_tiles = p->xt && p->p3_tiles;                      // pass 3 reads the resident tiled copy: nobody needs the batch copy
+        uint8_t* xg = (h == 0 && hd.CP <= 8 && !p3_tiles) ? d.xg : nullptr;          // head 0's launch leaves the batch copy for pass 3
         nadm_adam_t ad;
         const nadm_adam_t* adp = nullptr;
         if (lr_scale) { ad = adam_at(p, p->lay.off_p[h], lr_scale[0], p->step_count, lr_scale[1]); adp = &ad; }
@@ -405,7 +416,7 @@ int decode_heads(nadm_plan* p, const int32_t* idx, int b, int with_loss, const f
         // sliced / from the Q images / splitting Q itself, in the plan's precision; "highest" is refused in the words of the public form
         // of the same shape (nadm_decode_bce_sliced / _images / _step), "medium" in the step's own
         const bool medium = p->precision == NADM_PRECISION_MEDIUM;
-        Pass2Launch a{d.xp, d.ld, idx, b, d.M, Ph, kp, Qh, hd.SP, dPh, slab, lossp, flags, xg, qi, slices,
+        Pass2Launch a{x_of(p, qi != nullptr), idx, b, d.M, Ph, kp, Qh, hd.SP, dPh, slab, lossp, flags, xg, qi, slices,
                       slices > 1 ? d.p2_slab + p->slab_off[h] : nullptr, slices > 1 ? d.p2_cnt + p->loss_off[h] : nullptr, medium, st};
         const char* who = medium ? "nadm_step" : slices > 1 ? "nadm_decode_bce_sliced" : qi ? "nadm_decode_bce_images" : "nadm_decode_bce_step";
         if (pass2_step_args(a, who, adp, !medium && slices <= 1 && !qi) || pass2(a)) return 1;
@@ -457,7 +468,7 @@ extern "C" int nadm_plan_create(const nadm_plan_desc_t* desc, nadm_plan_t** out)
     if (!d.params || !d.grads || !d.m || !d.v || !d.zpart || !d.Z || !d.rinv || !d.Zn || !d.H || !d.Q || !d.dL || !d.dHpre || !d.dgp || !d.dZ ||
         !d.dqpart || !d.losspart || !d.small_part || !d.loss_acc)
         return fail("nadm_plan_create: null pointer in the descriptor");
-    if (hd.CP <= 8 && (!d.dzimg || !d.dzcnt || !d.xg)) return fail("nadm_plan_create: C <= 8 needs dzimg, dzcnt and xg");
+    if (hd.CP <= 8 && (!d.dzimg || !d.dzcnt)) return fail("nadm_plan_create: C <= 8 needs dzimg and dzcnt");      // (xg: see nadm_step)
     if (d.mode == NADM_MODE_SNP && (!d.zsum || !d.dqsum)) return fail("nadm_plan_create: SNP mode needs zsum and dqsum");
     if (d.mode == NADM_MODE_SINGLE && d.comm && d.comm->world != 1) return fail("nadm_plan_create: single mode with a communicator of several ranks");
     for (const nadm_comm_t* c : {d.comm, d.comm_a})
@@ -535,6 +546,17 @@ extern "C" void nadm_plan_destroy(nadm_plan_t* p) {
 extern "C" int nadm_plan_set_rows(nadm_plan_t* p, const uint8_t* xp) {
     if (!p || !xp) return fail("nadm_plan_set_rows: null pointer");
     p->d.xp = xp;
+    p->xt = nullptr; p->xt_rows = 0; p->p3_tiles = false;        // a copy of other rows is no copy of these
+    return 0;
+}
+
+extern "C" int nadm_plan_set_tiles(nadm_plan_t* p, const uint8_t* xt, int64_t rows, int32_t pass3_too) {
+    if (!p) return fail("nadm_plan_set_tiles: null pointer");
+    if (p->poisoned) return poisoned(p, "nadm_plan_set_tiles");
+    if (xt && !p->d.xp) return fail("nadm_plan_set_tiles: the tiled copy goes with the rows it copies (nadm_plan_set_rows first)");
+    if (xt && (rows <= 0 || (rows >> 31))) return fail("nadm_plan_set_tiles: rows must be in 1 .. 2^31 - 1");
+    if ((uintptr_t)xt & 15) return fail("nadm_plan_set_tiles: the tiled copy must be 16-byte aligned");
+    p->xt = xt; p->xt_rows = xt ? rows : 0; p->p3_tiles = xt && pass3_too != 0;
     return 0;
 }
 
@@ -668,7 +690,10 @@ static int step_impl(nadm_plan_t* p, const int32_t* idx, int32_t b, float lr, in
     float* V = d.params + p->lay.off_v;
     float* dV = d.grads + p->lay.off_v;
     const int splits = nadm_sample_splits(b);
-    const int p3_flags = image ? NADM_X_CLEAN : 0;
+    const bool p3_tiles = image && p->xt && p->p3_tiles;         // pass 3 gathers from the resident tiled copy; else from pass 2's batch copy
+    if (image && !p3_tiles && !d.xg) return fail("nadm_step: C <= 8 needs the batch copy (nadm_plan_desc_t.xg) unless pass 3 reads the tiled copy (nadm_plan_set_tiles)");
+    const int p3_flags = image && !p3_tiles ? NADM_X_CLEAN : 0;
+    const XSource x3 = p3_tiles ? x_tiled(p->xt, p->xt_rows) : x_rows(image ? d.xg : d.xp, d.ld);
     if (dp) {
         // Message B.  n_buckets > 1, bucket by bucket (DDP's bucketed exchange, neural_admixture.py:315-319): pass 3 is launched range by range; behind
         // range j the side stream sums bucket j over the ranks, updates this rank's slice and gathers the range -- while the compute
@@ -687,8 +712,8 @@ static int step_impl(nadm_plan_t* p, const int32_t* idx, int32_t b, float lr, in
         for (int j = 0; j < p->nb; ++j) {
             if (parts || j == 0) {
                 const int64_t m0 = parts ? p->lay.bkt_m0[j] : 0, m1 = parts ? p->lay.bkt_m0[j + 1] : d.M;
-                const uint8_t* xsrc = image ? d.xg + (m0 / 4) * (int64_t)b : d.xp + m0 / 4;
-                Pass3Launch a{xsrc, d.ld, idx, b, m1 - m0, d.dZ, image ? d.dzimg : nullptr, hd.CP, V + m0 * hd.CP, dV + m0 * hd.CP, j == 0 ? &mw : nullptr,
+                const XSource xsrc = p3_tiles ? x_from_snp(x3, m0) : x_rows(image ? d.xg + (m0 / 4) * (int64_t)b : d.xp + m0 / 4, d.ld);
+                Pass3Launch a{xsrc, idx, b, m1 - m0, d.dZ, image ? d.dzimg : nullptr, hd.CP, V + m0 * hd.CP, dV + m0 * hd.CP, j == 0 ? &mw : nullptr,
                               p3_flags, 0u, 1, nullptr, nullptr, stream};
                 if (pass3_step_args(a, "nadm_encode_bwd_step", nullptr, false) || pass3(a)) return 1;
                 if (!parts || j == p->nb - 1) { if (t4.end()) return 1; }
@@ -720,7 +745,7 @@ static int step_impl(nadm_plan_t* p, const int32_t* idx, int32_t b, float lr, in
     const int p3_slices = (d.p3_slab && image) ? nadm_encode_slices(b, d.M, hd.CP) : 1;      // sample slices where the SNP chunks alone leave CUs idle
     if (p3_slices > p->p3_slices_cap) return fail("nadm_step: pass 3 would be cut into more sample slices than the plan's slab was sized for at creation");
     const bool p3_sliced = p3_slices > 1;                        // (then image holds: the sliced form's operands are the unsliced form's)
-    Pass3Launch a3{image ? d.xg : d.xp, d.ld, idx, b, d.M, d.dZ, image ? d.dzimg : nullptr, hd.CP, V, dV, &mw, p3_flags, 0u, p3_slices,
+    Pass3Launch a3{x3, idx, b, d.M, d.dZ, image ? d.dzimg : nullptr, hd.CP, V, dV, &mw, p3_flags, 0u, p3_slices,
                    p3_sliced ? d.p3_slab : nullptr, p3_sliced ? d.p3_cnt : nullptr, stream};
     if (pass3_step_args(a3, p3_sliced ? "nadm_encode_bwd_sliced" : "nadm_encode_bwd_step", &av, p3_sliced) || pass3(a3)) return 1;
     if (t4.end()) return 1;

@@ -69,6 +69,17 @@ def final_q(eng, n: int, b: int) -> List[torch.Tensor]:
     return [torch.cat(q, dim=0) for q in zip(*parts)]
 
 
+RESIDENT_PASS3 = True       # pass 3 reads the resident tiled copy too and pass 2 writes no batch copy (Engine(resident_pass3=...)): the measured decision, DESIGN.md 4.2
+
+
+def _copy_fits(device: torch.device, need: int) -> bool:
+    """Is there room for `need` more bytes beside what the device already holds?  Free memory as the driver sees it plus what torch's
+    allocator holds unused, less a twentieth of the device for the step's buffers and the analyses' scratch."""
+    free, total = torch.cuda.mem_get_info(device)
+    cached = torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+    return free + cached - need >= total // 20
+
+
 class Engine:
     @classmethod
     def supports(cls, device: torch.device) -> bool:
@@ -78,9 +89,17 @@ class Engine:
 
     def __init__(self, M: int, C_: int, Hd: int, ks: Sequence[int], device: torch.device, max_batch: int,
                  mode: str = "single", comm=None, n_buckets: int = 1, comm_a=None, p3_whole: bool = False, debug: bool = False,
-                 precision: str = "highest", ld: Optional[int] = None):
+                 precision: str = "highest", resident: str = "auto", resident_pass3: Optional[bool] = None, ld: Optional[int] = None):
+        """``resident``: where the step's matrix-core passes gather the batch from.  "tiled": a tiled, cleaned copy of the whole matrix that
+        set_packed makes once (nadm_tile_packed; as many bytes again as the matrix); "rows": the row-major matrix itself; "auto": the copy
+        when it fits beside the matrix (_copy_fits), else the rows.  Results are bit-identical.  ``resident_pass3``: pass 3 reads the copy
+        too and pass 2 writes no batch copy (None: RESIDENT_PASS3)."""
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'highest' or 'medium'")
+        if resident not in ("auto", "rows", "tiled"):
+            raise ValueError("resident must be 'auto', 'rows' or 'tiled'")
+        self.resident, self.resident_pass3 = resident, bool(RESIDENT_PASS3 if resident_pass3 is None else resident_pass3)
+        self._xt: Optional[torch.Tensor] = None         # the tiled copy of xp, while the plan reads it
         if not self.supports(device):
             raise RuntimeError("neural_admixture_amd.Engine needs a ROCm GPU device (no CPU fallback)")
         if mode not in _MODES:
@@ -124,7 +143,9 @@ class Engine:
         tiled = gpu and L.CP <= 8
         self._dzimg = torch.zeros(int(lib.nadm_dz_image_bytes(b)), dtype=torch.uint8, device=device) if tiled else None
         self._dzcnt = torch.zeros((b + 31) // 32, dtype=torch.int32, device=device)      # group counters of nadm_mlp_bwd_image
-        self._xg = torch.empty(int(lib.nadm_batch_copy_bytes(b, self.M)), dtype=torch.uint8, device=device) if tiled else None
+        # (no batch copy where pass 3 is sure to read the resident tiled copy)
+        need_xg = tiled and not (self.resident == "tiled" and self.resident_pass3)
+        self._xg = torch.empty(int(lib.nadm_batch_copy_bytes(b, self.M)), dtype=torch.uint8, device=device) if need_xg else None
         self._iota = torch.arange(b, dtype=torch.int32, device=device) if tiled else None
         # pass 2 in sample slices (include/nadm.h, nadm_decode_bce_sliced): where the SNP chunks alone leave CUs idle (M below ~330k)
         # every slice parks its partial of dP in a slab; one region per head, one counter per chunk
@@ -200,6 +221,7 @@ class Engine:
         per-step host sync; in "dp" / "snp" mode including the collectives)."""
         if b > self.bmax:
             raise RuntimeError("batch larger than the engine was sized for")
+        self._tiles_current()
         if lib.nadm_step(self._plan, ptr(idx), b, lr, 1 if with_loss else 0, _stream()):
             self._comm_error()
             check(1, "step")
@@ -250,8 +272,37 @@ class Engine:
         if xp.dtype != torch.uint8 or xp.dim() != 2 or xp.shape[1] != self.ld or not xp.is_contiguous():
             raise RuntimeError(f"packed genotypes must be contiguous uint8 [rows, {self.ld}]")
         self.xp = xp
+        self._xt = None
         if self._plan is not None:
             check(lib.nadm_plan_set_rows(self._plan, ptr(xp)), "plan_set_rows")
+            self._tile_resident()
+
+    def _tile_resident(self) -> None:
+        """The tiled, cleaned copy of self.xp for the plan's matrix-core passes (``resident``), made once per matrix: production hands the
+        matrix over once and trains for hundreds of epochs on it.  self.xp stays the caller's row-major tensor; every analysis reads it."""
+        L = self.lay
+        if self.resident == "rows" or not (L.CP <= 8 or self.qimg is not None):      # (no matrix-core pass: nobody would read it)
+            return
+        rows = int(self.xp.shape[0])
+        need = int(lib.nadm_tiled_bytes(rows, self.M))
+        if rows == 0:
+            return
+        if self._xt is not None and self._xt.numel() == need:
+            xt = self._xt                                # the same matrix, written in place: the copy is made again where it is
+        elif self.resident == "auto" and not _copy_fits(self.device, need):
+            return
+        else:
+            xt = torch.empty(need, dtype=torch.uint8, device=self.device)
+        check(lib.nadm_tile_packed(ptr(self.xp), self.ld, rows, self.M, ptr(xt), _stream()), "tile_packed")
+        check(lib.nadm_plan_set_tiles(self._plan, ptr(xt), rows, 1 if (self.resident_pass3 and L.CP <= 8) else 0), "plan_set_tiles")
+        self._xt, self._xt_version = xt, self.xp._version
+
+    def _tiles_current(self) -> None:
+        """The matrix is a live operand of the step: a caller that wrote into self.xp in place since the copy was made (torch counts the
+        writes of a tensor and of its views) gets the copy made again, on the stream the step is queued on.  Training never does -- the
+        check is one attribute read per step.  (A write through a raw pointer is invisible to it: call set_packed again.)"""
+        if self._xt is not None and self.xp._version != self._xt_version:
+            self._tile_resident()
 
     def pack_from_host(self, data_u8: torch.Tensor, rows: Optional[np.ndarray] = None, chunk_rows: Optional[int] = None) -> None:
         """uint8 [N,M] CPU tensor -> packed rows in HBM.  Packs on the host (2 bits/genotype cross PCIe instead of 8; the
@@ -537,6 +588,7 @@ class Engine:
         """Encoder-only pass (final Q, neural_admixture.py:369-383; src/inference.py:71-77)."""
         L = self.lay
         if self._plan is not None:
+            self._tiles_current()
             if lib.nadm_plan_infer(self._plan, ptr(idx), b, _stream()):
                 self._comm_error()
                 check(1, "plan_infer")

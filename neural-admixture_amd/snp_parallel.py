@@ -39,13 +39,13 @@ class SnpShardedEngine(Engine):
     torch.distributed process group the result gathers and the loss read-back use (None = default)."""
 
     def __init__(self, M_total: int, C_: int, Hd: int, ks: Sequence[int], device: torch.device, max_batch: int,
-                 comm=None, group=None, precision: str = "highest"):
+                 comm=None, group=None, precision: str = "highest", **resident):
         self.M_total, self.group = int(M_total), group
         world, rank = (comm.world, comm.rank) if comm is not None else (1, 0)
         self.m0, self.m1 = snp_slices(self.M_total, world)[rank]
         if self.m1 <= self.m0:
             raise RuntimeError(f"SNP-sharded run: rank {rank} of {world} would own no SNPs (M = {M_total})")
-        super().__init__(self.m1 - self.m0, C_, Hd, ks, device, max_batch, mode="snp", comm=comm, precision=precision)
+        super().__init__(self.m1 - self.m0, C_, Hd, ks, device, max_batch, mode="snp", comm=comm, precision=precision, **resident)     # (resident=, resident_pass3=: the tiled copy of this rank's slice)
 
     # ------------------------------------------------------------------ data / parameters: slice, then as the base class
     def pack_from_host(self, data_u8, rows=None, chunk_rows=None) -> None:
