@@ -772,6 +772,41 @@ int nadm_select_snps(const uint8_t* xp, int64_t ld_in, int64_t rows, const int64
 int nadm_ld_sweep(const double* r2, int64_t m0, int64_t m1, int32_t W, int64_t M, const double* maf, const int32_t* chrom,
                   double thr, uint8_t* kept);
 
+/* ---- Admixture dating: weighted admixture LD summed into bins of genetic distance -------------------------------------------------
+ * The covariance of the genotypes at two SNPs, weighted at each SNP by the allele-frequency difference of the two sources, decays
+ * as exp(-n d) with the genetic distance d for an admixture n generations ago (ROLLOFF, Moorjani et al. 2011; ALDER, Loh et al.
+ * 2013).  nadm_wld sums that statistic over EVERY pair of SNPs within reach, exactly, on the packed matrix already in HBM; the
+ * binning grid, the weights, the fit and its jackknife are the caller's (admixdate.py).
+ *
+ * Rows: idx[0..rows) (idx == NULL: rows 0..rows; any order, a duplicate counts as often as it occurs), rows in 2..2^24.
+ * Pairs: every (a, b) with m0 <= a < b < m1 and b - a <= W.  cell int32 [M], values >= 0 and nondecreasing: a SNP's genetic
+ * position on a grid of one bin width; the bin of a pair is cell[b] - cell[a], a pair with a bin >= nbins is dropped.  (A caller
+ * with several chromosomes calls once per chromosome range and leaves a gap of more than nbins cells between them.)
+ * wt double [C, M], curve-major, C in 1..NADM_WLD_MAX_CURVES; nmin >= 2.
+ *
+ * Moments, over the rows where BOTH calls are observed, as nadm_ld_band defines them:
+ *     n = sum o_a o_b      Sa = sum g_a o_b      Sb = sum o_a g_b      Sab = sum g_a g_b
+ * on the matrix pipe (v_mfma_i32_16x16x64_i8, samples on its k axis; per side the two int8 pieces o and g o), int32 and EXACT.  The
+ * pad bits of a row's last byte, rows beyond `rows` and SNPs >= M enter as the missing code.  A pair with n < nmin is skipped.
+ * Per counted pair, in this order, every step ONE IEEE float64 operation, nothing contracted:
+ *     v = (double)(n Sab - Sa Sb) / (double)(n (n - 1))          numerator and denominator formed in int64: the unbiased covariance
+ *     t = ((v * wt[c][a]) * wt[c][b]) * 2^32                       for every curve c
+ *     q = llrint(t)                                               round to nearest, ties to even
+ * Outputs: sum int64 [C, nbins], sum[c][bin] = the sum of q over the bin's pairs; cnt int64 [nbins], the pairs counted per bin.
+ * Both are zeroed here.  The sums are integers added with 64-bit integer atomics: the same inputs give the same bits in any order;
+ * no floating-point atomics, no scratch.
+ * Overflow: |v| <= 2 always, and the caller promises |wt| <= 1, so |q| <= 2^33: ONE call may add at most 2^29 pairs to one bin
+ * (check cnt after the call); the rounding moves a bin's mean, sum / cnt / 2^32, by less than 2^-33.
+ * The reader's 0 <-> 2 flip of a SNP leaves the statistic unchanged when the weights are taken from frequencies of the same
+ * orientation: the covariance changes sign and so does that SNP's weight.
+ * W in 1..NADM_WLD_MAX_SPAN, nbins in 1..NADM_WLD_MAX_BINS, 0 <= m0 < m1 <= M; ld >= ceil(M/4), ld % 16 == 0, ld < 2^32; xp 16-byte,
+ * wt / sum / cnt 8-byte, cell / idx 4-byte aligned.  Every refusal is reported before anything is launched.  Asynchronous on `stream`. */
+#define NADM_WLD_MAX_CURVES 32
+#define NADM_WLD_MAX_BINS 4096
+#define NADM_WLD_MAX_SPAN 65536
+int nadm_wld(const uint8_t* xp, int64_t ld, const int32_t* idx, int64_t rows, int64_t M, int64_t m0, int64_t m1, int32_t W,
+             const int32_t* cell, const double* wt, int32_t C, int32_t nbins, int32_t nmin, int64_t* sum, int64_t* cnt, void* stream);
+
 /* ---- Hardy-Weinberg proportions given ancestry: the per-SNP score test of an inbreeding coefficient ----------------------------
  * The likelihood itself is the model's third assumption: a genotype is binomial(2, pi_ij), i.e. Hardy-Weinberg proportions GIVEN the
  * sample's ancestry.  SNPs that break it (heterozygote drop-out, paralogs, batch effects) bias P and Q; plink's plain --hwe rejects

@@ -155,6 +155,7 @@ def _load():
         "nadm_ld_band": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp]),
         "nadm_select_snps": (C.c_int, [vp, i64, i64, vp, i64, i32, vp, i64, vp]),
         "nadm_ld_sweep": (C.c_int, [vp, i64, i64, i32, i64, vp, vp, C.c_double, vp]),
+        "nadm_wld": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
         "nadm_savetxt_f32": (C.c_int, [C.c_char_p, vp, i64, i64, i64]),
         "nadm_gmm_fit_means": (C.c_int, [vp, i64, i32, i32, vp, i32, C.c_double, i32, C.c_double, vp, C.POINTER(C.c_double), C.POINTER(i32)]),
         "nadm_gmm_fit_means_dev": (C.c_int, [vp, i64, i32, i32, vp, i32, C.c_double, i32, C.c_double, vp, C.POINTER(C.c_double), C.POINTER(i32), vp]),

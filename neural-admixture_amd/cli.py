@@ -1,4 +1,4 @@
-"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|king|kinship|prune|hwe|cv|bootstrap|pse|qse|fit|pca|residpca ...``.
+"""Thin command line with the reference's flags (entry.py:20-67): ``python -m neural_admixture_amd train|infer|king|kinship|prune|hwe|cv|bootstrap|pse|qse|fit|pca|residpca|date ...``.
 Reads BED input straight into the packed layout, runs the RSVD + GMM initialisation, trains on the MI355X engine and
 writes ``{name}.{K}.Q/.P``, ``{name}.pt`` and ``{name}_config.json`` exactly where the reference does
 (src/main.py:38-44, src/inference.py:91-92).  BED and VCF inputs are read natively (io.read_bed_packed, io.read_vcf_packed);
@@ -20,7 +20,7 @@ import torch
 
 from .engine import row_ranges
 from .train import AFTER_KEYWORDS, AFTER_TRAINING
-from .io import (chrom_codes, find_run_files, read_bim, read_fam, read_id_list, read_run_matrix, read_sample_list, resolve_ids,
+from .io import (chrom_codes, find_run_files, genetic_map, read_bim, read_bim_map, read_fam, read_id_list, read_run_matrix, read_sample_list, resolve_ids,
                  resolve_samples, write_id_list)
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(message)s")
@@ -253,6 +253,32 @@ def parse_hwe_args(argv):
                         "call counts); the score is heavy-tailed for rare variants, 0.01 to 0.05 guards against that")
     p.add_argument("--alpha", type=float, default=1e-6,
                    help="a SNP whose two-sided p-value is below this goes to the .hwe.out list (default 1e-6, plink's customary --hwe threshold)")
+    return p.parse_args(argv)
+
+
+def parse_date_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture date",
+                                description="Admixture dating: the decay of weighted admixture LD with genetic distance (ROLLOFF / "
+                                            "ALDER's statistic, summed over every SNP pair), from a run's .P and .Q files and the "
+                                            "genetic map of the .bim.  Use data that was NOT LD-pruned")
+    _add_run_args(p, multi_k=True, out="curves and dates")
+    p.add_argument("--pops_path", type=str, default=None, metavar="FILE",
+                   help="one group label per sample of the .fam; with --target, the samples to date")
+    p.add_argument("--target", type=str, default=None, metavar="LABEL",
+                   help="date the samples whose line of --pops_path is LABEL (default: every sample left after --keep / --remove)")
+    p.add_argument("--min_share", type=float, default=0.05,
+                   help="a curve is computed for every pair of components whose two mean shares in the group are both at least this (default 0.05)")
+    p.add_argument("--pairs", type=str, default=None, metavar="a-b,...",
+                   help="the component pairs to date, 1-based like the columns of the .Q file (e.g. 1-3,2-3), instead of --min_share's choice")
+    p.add_argument("--binsize", type=float, default=0.05, help="bin width in cM (default 0.05, ALDER's convention)")
+    p.add_argument("--mindist", type=float, default=0.5,
+                   help="fit from this distance in cM on (default 0.5, ALDER's convention: background LD inside the sources sits below that)")
+    p.add_argument("--maxdist", type=float, default=20.0, help="fit up to this distance in cM (default 20, ALDER's convention)")
+    p.add_argument("--morgans", action="store_true", help="column 3 of the .bim is in Morgans (default: cM)")
+    p.add_argument("--rate", type=float, default=1.0, metavar="CM_PER_MB",
+                   help="where column 3 of the .bim is all zero: this many cM per Mb applied to the base-pair column (default 1.0); the "
+                        "date scales with it")
+    p.add_argument("--nmin", type=int, default=2, help="leave out a SNP pair with fewer jointly observed samples than this (default 2)")
     return p.parse_args(argv)
 
 
@@ -793,6 +819,86 @@ def _residpca_main(argv):
     log.info("    Residual eigenvalues and eigenvectors saved.")
 
 
+def _date_main(argv):
+    """``date`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes and the genetic map of the .bim ->
+    {out_name}.{K}.wld (``d_cM pairs`` and one column per curve, a row per bin) and {out_name}.{K}.date (``a b generations se A se_A c
+    z`` per curve), and a line per curve in the log."""
+    from . import admixdate
+    args = parse_date_args(argv)
+    ks = _ks_asked(args)
+    try:
+        nbins = admixdate.check_args(args.binsize, args.mindist, args.maxdist, args.min_share)
+    except RuntimeError as e:
+        raise SystemExit(f"    {e}.") from None
+    if not args.rate > 0.0:
+        raise SystemExit("    --rate must be > 0 (cM per Mb).")
+    if args.nmin < 2:
+        raise SystemExit("    --nmin must be >= 2.")
+    if args.target is not None and args.pops_path is None:
+        raise SystemExit("    --target names a label of --pops_path: give that file.")
+    pairs = None
+    if args.pairs is not None:
+        try:
+            pairs = [tuple(int(v) - 1 for v in item.split("-")) for item in args.pairs.split(",")]
+            ok = all(len(pr) == 2 and pr[0] != pr[1] and 0 <= min(pr) and max(pr) < min(ks) for pr in pairs)
+        except ValueError:
+            ok = False
+        if not ok or len(pairs) < 1:
+            raise SystemExit(f"    --pairs takes component pairs like 1-2,1-3: two different components in 1..{min(ks)} each.")
+    _need_bed(args.data_path, "date needs the genetic map of a .bim file")
+    labels = None
+    if args.pops_path is not None:
+        if not os.path.isfile(args.pops_path):
+            raise SystemExit(f"    {args.pops_path} not found.")
+        with open(args.pops_path, "r") as fb:
+            labels = [ln.strip() for ln in fb.read().splitlines()]
+    paths = _find_run_heads(args, ks, "date")              # before anything is read
+    _, _, bim, _, chroms = _bed_ids(args.data_path)        # before the GPU check and before any genotype is read
+    cm, from_rate = genetic_map(*read_bim_map(bim), morgans=args.morgans, rate=args.rate)
+    keep = _extract_keep(args.data_path, args.extract)
+    chrom = chrom_codes(chroms)
+    if keep is not None:                                   # the map follows the kept SNPs
+        cm, chrom = cm[keep], chrom[keep]
+    try:
+        admixdate.grid_cells(cm, chrom, args.binsize, nbins)
+    except RuntimeError as e:
+        raise SystemExit(f"    {bim}: {e}.") from None
+    group = None
+    if labels is not None:
+        labels = _filter_lines(labels, _sample_keep(args), args.pops_path)
+        if args.target is not None:
+            group = np.asarray([lb == args.target for lb in labels], dtype=bool)
+            if int(group.sum()) < 2:
+                raise SystemExit(f"    --target {args.target}: {int(group.sum())} samples of {args.pops_path} carry that label; a "
+                                 "covariance needs at least 2.")
+
+    def check_n(n):
+        if labels is not None and len(labels) != n:
+            raise SystemExit(f"    {args.pops_path} lists {len(labels)} labels, the data holds {n} samples.")
+        if n < 2:
+            raise SystemExit("    date needs at least 2 samples.")
+    data, Ps, Qs = _load_run_heads(args, ks, paths, keep, check_n)
+    if from_rate:
+        log.info(f"    Warning: column 3 of {bim} is all zero; the genetic map is {args.rate:g} cM per Mb of column 4, and every date "
+                 "scales with that rate.")
+    if keep is not None:
+        log.info("    Warning: --extract is in use; if the list is LD-pruned, pruning has removed the signal that is dated here: run "
+                 "date on the unpruned SNPs.")
+    idx = None if group is None else torch.from_numpy(np.nonzero(group)[0].astype(np.int32)).to(data.packed.device)
+    log.info(f"    Admixture dating of {data.N if group is None else int(group.sum())} samples: weighted LD in {nbins} bins of "
+             f"{args.binsize:g} cM, fitted over [{args.mindist:g}, {args.maxdist:g}) cM, jackknife over {len(set(chrom.tolist()))} chromosomes.")
+    for k, P, Q in zip(ks, Ps, Qs):
+        try:
+            res = admixdate.admix_date(data.packed, data.M, P, Q if group is None else Q[group], cm, chrom, idx=idx, pairs=pairs,
+                                       binsize=args.binsize, dmin=args.mindist, maxdist=args.maxdist, min_share=args.min_share,
+                                       nmin=args.nmin)
+        except RuntimeError as e:
+            raise SystemExit(f"    K={k}: {e}.") from None
+        admixdate.log_results(res, k, log)
+        admixdate.write_results(os.path.dirname(_out_stem(args)), args.out_name or args.name, k, res)
+    log.info("    Weighted LD curves and dates saved.")
+
+
 def _king_main(argv):
     """``king`` mode: the genotypes alone -> {name}.king (``i j phi n hethet ibs0`` per pair at or above --cutoff, 0-based indices
     among the samples analysed, by i then j) and {name}.king.in / .king.out, the kept and the removed samples of ``king.unrelated_set`` as ``FID IID``
@@ -932,14 +1038,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 
 _ANALYSIS_MODES = {"king": _king_main, "kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
-                   "pse": _pse_main, "qse": _qse_main, "fit": _fit_main, "pca": _pca_main, "residpca": _residpca_main}
+                   "pse": _pse_main, "qse": _qse_main, "fit": _fit_main, "pca": _pca_main, "residpca": _residpca_main, "date": _date_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "qse", "fit", "pca", "residpca"), \
+    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "qse", "fit", "pca", "residpca", "date"), \
         ('Please provide either the argument "train" or "infer" to choose running mode ("king" finds relatives before a run, "kinship", "prune" and "hwe" check a run\'s assumptions, '
-         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "qse" on Q given P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes, "residpca" those of the model\'s residuals).')
+         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "qse" on Q given P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes, "residpca" those of the model\'s residuals, "date" dates the admixture from the decay of weighted LD).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         _ANALYSIS_MODES[mode](argv[1:])

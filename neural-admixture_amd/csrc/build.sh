@@ -26,6 +26,7 @@ X="$*"
 #   nadm_ibd          IBD-sharing sums given ancestry (k0 / k1 / k2) from Q, P and f on the matrix pipe (nadm_ibd; not on the training path)
 #   nadm_king         KING-robust kinship counts from the genotypes alone on the matrix pipe (nadm_king; not on the training path)
 #   nadm_ld           LD pruning: windowed r^2 on the matrix pipe, SNP counts, SNP selection (not on the training path)
+#   nadm_wld          admixture dating: weighted LD summed into bins of genetic distance on the matrix pipe (nadm_wld; not on the training path)
 #   nadm_snp_hwe      Hardy-Weinberg score test given ancestry, per SNP (nadm_snp_hwe; not on the training path)
 #   nadm_cv           cross-validation over held-out calls: the masked copy and the held-out deviance (not on the training path)
 #   nadm_snp_info     standard errors of P: per-SNP Fisher information given Q (nadm_snp_info; not on the training path)
@@ -54,6 +55,7 @@ $X $FLAGS -c nadm_kinship.hip -o $obj/nadm_kinship.o
 $X $FLAGS -c nadm_ibd.hip -o $obj/nadm_ibd.o
 $X $FLAGS -c nadm_king.hip -o $obj/nadm_king.o
 $X $FLAGS -c nadm_ld.hip -o $obj/nadm_ld.o
+$X $FLAGS -c nadm_wld.hip -o $obj/nadm_wld.o
 $X $FLAGS -c nadm_snp_hwe.hip -o $obj/nadm_snp_hwe.o
 $X $FLAGS -c nadm_cv.hip -o $obj/nadm_cv.o
 $X $FLAGS -c nadm_snp_info.hip -o $obj/nadm_snp_info.o
@@ -69,7 +71,7 @@ $X $HOST -c nadm_ld_sweep.cpp -o $obj/nadm_ld_sweep.o
 $X $HOST -c nadm_hooks.cpp -o $obj/nadm_hooks.o
 $X $HOST -DNADM_TEST_HOOKS -c nadm_hooks.cpp -o $obj/nadm_hooks_th.o
 UNITS
-OBJS="nadm_genotype_passes.o nadm_small_kernels.o nadm_step.o nadm_passes_host.o nadm_gmm.o nadm_gmm_dev.o nadm_calib.o nadm_project.o nadm_project_p.o nadm_kinship.o nadm_ibd.o nadm_king.o nadm_ld.o nadm_snp_hwe.o nadm_cv.o nadm_snp_info.o nadm_sample_info.o nadm_resid_cor.o nadm_obs_project.o nadm_resid_project.o nadm_host_io.o nadm_layout.o nadm_ld_sweep.o"
+OBJS="nadm_genotype_passes.o nadm_small_kernels.o nadm_step.o nadm_passes_host.o nadm_gmm.o nadm_gmm_dev.o nadm_calib.o nadm_project.o nadm_project_p.o nadm_kinship.o nadm_ibd.o nadm_king.o nadm_ld.o nadm_wld.o nadm_snp_hwe.o nadm_cv.o nadm_snp_info.o nadm_sample_info.o nadm_resid_cor.o nadm_obs_project.o nadm_resid_project.o nadm_host_io.o nadm_layout.o nadm_ld_sweep.o"
 cd "$obj"
 link="hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-soname,libnadm.so"
 if [ -n "$out" ]; then

@@ -765,6 +765,22 @@ class Engine:
                        max_k=(residpca.MAX_K, residpca.TOO_WIDE))
         return residpca.resid_pca(self.xp, self.M, *self._fitted(head), pcs=pcs, oversample=oversample, iters=iters, pimin=pimin, seed=seed)
 
+    def admix_date(self, cm, chrom, head: int = 0, idx: Optional[torch.Tensor] = None, pairs=None, binsize: Optional[float] = None,
+                   dmin: Optional[float] = None, maxdist: Optional[float] = None, min_share: Optional[float] = None, nmin: int = 2):
+        """The date of the admixture of one sample group of the resident matrix -- the rows ``idx`` (int32, default: all) -- from the
+        decay of its weighted admixture LD with the genetic distance (admixdate.admix_date; include/nadm.h, nadm_wld): the curves
+        of the component pairs ``pairs`` (default: those with a mean share of ``min_share`` each in the group) weighted with head
+        ``head``'s P, on the genetic map ``cm [M]`` (cM) and the chromosomes ``chrom [M]``.  A ``DateCurves`` with one ``DateResult``
+        per curve (generations, jackknife standard errors over the chromosomes, z of the amplitude).  The defaults are ALDER's
+        conventions.  The engine's parameters and optimiser state are left as they are."""
+        from . import admixdate as ad
+        self._analysis("admix_date", "use admixdate.admix_date on one GPU from the written .P and .Q files", head=head)
+        P, Q = self._fitted(head)
+        return ad.admix_date(self.xp, self.M, P, Q if idx is None else Q[idx.long()], cm, chrom, idx=idx, pairs=pairs,
+                             binsize=ad.BINSIZE if binsize is None else binsize, dmin=ad.DMIN if dmin is None else dmin,
+                             maxdist=ad.MAXDIST if maxdist is None else maxdist,
+                             min_share=ad.MIN_SHARE if min_share is None else min_share, nmin=nmin)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()

@@ -256,6 +256,33 @@ def read_bim(path) -> tuple:
     return ids, chroms
 
 
+def read_bim_map(path) -> tuple:
+    """A PLINK ``.bim`` -> ``(cm, bp)``: column 3 (the genetic position, as the file gives it) as float64 and column 4 (the base-pair
+    position) as int64, in file order.  A line with fewer than four columns or a field that is not a number ends the run, naming it."""
+    cm, bp = [], []
+    with open(path) as fb:
+        for ln, line in enumerate(fb, 1):
+            f = line.split()
+            if len(f) < 4:
+                raise SystemExit(f"    {path}: line {ln} has fewer than four columns.")
+            try:
+                cm.append(float(f[2]))
+                bp.append(int(f[3]))
+            except ValueError:
+                raise SystemExit(f"    {path}: line {ln} holds a genetic or base-pair position that is not a number.") from None
+    return np.asarray(cm, dtype=np.float64), np.asarray(bp, dtype=np.int64)
+
+
+def genetic_map(cm, bp, morgans: bool = False, rate: float = 1.0) -> tuple:
+    """The genetic positions in cM from ``read_bim_map``'s columns -> ``(cm, from_rate)``: column 3 as it is, times 100 with ``morgans``;
+    where that column is all zero, ``rate`` cM per Mb applied to the base-pair column (``from_rate`` True: a date then scales with
+    that rate)."""
+    cm = np.asarray(cm, dtype=np.float64)
+    if len(cm) and not np.any(cm != 0.0):
+        return np.asarray(bp, dtype=np.float64) * (float(rate) / 1e6), True
+    return (cm * 100.0 if morgans else cm.copy()), False
+
+
 def chrom_codes(chroms) -> np.ndarray:
     """Chromosome labels -> int32 codes, equal labels equal codes (numbered by first appearance)."""
     seen = {}

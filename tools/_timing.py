@@ -1,4 +1,4 @@
-"""What the time_*.py scripts of the analysis modes share (time_cv, time_bootstrap, time_pse, time_qse, time_residpca, time_fitcheck, time_pca, time_king, time_ibd): a resident synthetic
+"""What the time_*.py scripts of the analysis modes share (time_cv, time_bootstrap, time_pse, time_qse, time_residpca, time_fitcheck, time_pca, time_king, time_ibd, time_wld): a resident synthetic
 matrix drawn from a model, the quartiles of a leg's times and the device-event clock.  Imported as a sibling module: the scripts run as
 ``python tools/time_x.py``."""
 import numpy as np
