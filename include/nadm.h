@@ -965,6 +965,56 @@ int nadm_sample_info(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t 
                      const float* P, int32_t k, int32_t kp, const float* Q, int32_t q_stride,
                      float eps, double* info, int32_t* nobs, float* scratch, void* stream);
 
+/* ---- Local ancestry: the linkage model's forward-backward recursion along the genome ------------------------------------------------
+ * Which stretches of a sample's genome come from which component.  The linkage model of STRUCTURE (Falush, Stephens & Pritchard
+ * 2003), unphased as in ancestry_HMM (Corbett-Detig & Nielsen 2017): each of a sample's two haplotypes carries an ancestry, redrawn
+ * from the sample's q_i. with probability rho[j] between SNP j - 1 and j (the caller's 1 - exp(-n d): n generations, d Morgans,
+ * ONE rate for all components), and the call is emitted from the two ancestries' frequencies.  The hidden state is the unordered
+ * pair of ancestries: K (K + 1) / 2 states per sample, a dependent step per SNP, N M K^2 work.
+ * Rows, idx, P [M, kp], Q [b, k], q_stride, eps, the alignment and the ld rules are those of nadm_sample_info.  A segment s is the SNP
+ * range [seg[s], seg[s + 1]) (normally one chromosome); segments are independent and their bounds need not be multiples of 4 or 256;
+ * an empty one has ll = 0.  rho float [M] in [0, 1]; rho at a segment's first SNP is ignored (a restart).  out_snp int32 [n_out]
+ * strictly ascending: the SNPs at which the posterior is wanted; oseg int32 [n_seg + 1]: segment s owns out_snp[oseg[s] .. oseg[s + 1]),
+ * each inside the segment.  seg, oseg and out_snp live on the device and CANNOT be checked here: the caller validates them on the host
+ * before the upload (neural_admixture_amd/localanc.py: seg ascending within 0..M, out_snp strictly ascending, every slice inside its
+ * segment, oseg ascending from 0 to n_out); a slice that leaves 0..n_out is cut to it, so nothing is written outside the buffers.
+ * Per SNP j, all fp32, the symmetric a(x, y) held as its upper triangle x <= y < kp, a-major:
+ *     p_x = clip(P[j,x], eps, 1 - eps);   c_x = clip(1 - P[j,x], eps, 1 - eps)      (c from the UNCLIPPED value, as nadm_project_p)
+ *     e(x,y) = fma(u_x, v_y, u_y w_x):  code 0: c_x c_y;  code 1: fma(p_x, c_y, p_y c_x);  code 2: p_x p_y;  missing, j >= M: exactly 1
+ *     s = 1 - rho;  c0 = s s;  c1 = rho s;  c2 = rho rho              (a segment's first SNP: rho = 1 and a^ = 0, so pr = q_x q_y exactly)
+ *   forward, j ascending:
+ *     G_x = fma(c1, R_x, (c2 / 2) q_x);   pr(x,y) = fma(c0, a^(x,y), fma(q_y, G_x, q_x G_y))    (= c0 a^ + c1 (q_y R_x + q_x R_y) + c2 q_x q_y)
+ *     a = pr e;   R'_x = sum_y a(x,y), y ascending;   S = sum_x R'_x, x ascending (the sum over ORDERED pairs);
+ *     a^ = a rcp(S);   R_x = R'_x rcp(S);   ll += ln S;   at an output point a^ goes to the checkpoints
+ *   backward, j descending from the segment's last SNP, where b^ = sup, sup(x,y) = 1 where q_x q_y > 0, else 0:
+ *     at an output point  g = a^ b^;  D_x = sum_y g(x,y), y ascending;  Z = sum_x D_x;  dosage_x = min(2 (D_x rcp(Z)), 2);
+ *         the mass of the unordered pair is g(x,x) or 2 g(x,y); call = the a-major index over x <= y < k of the largest mass
+ *         (strictly: the lowest index wins a tie), post = that mass times rcp(Z)
+ *     from j to j - 1:  h = b^ e_j;  H_x = sum_y q_y h(x,y) (multiply-adds, y ascending);  Tt = sum_x q_x H_x;
+ *         J_x = fma(c1, H_x, (c2 / 2) Tt);  b(x,y) = sup (fma(c0, h, J_x + J_y)) with rho[j]    (= sup (c0 h + c1 (H_x + H_y) + c2 Tt));
+ *         b^ = b rcp(diagonal sum + 2 x upper sum, each a-major)
+ * The sup mask is part of the contract: without it a sample whose q has exact zeros and whose calls disagree with it over a long
+ * stretch underflows the supported states against the unsupported ones and ends in 0 / 0.  Where Z is 0 or not finite the point's
+ * dosage and post are NaN and call is 255; nothing is clipped silently.  rcp is the hardware's 1-ulp reciprocal; ln S is log2 S
+ * (v_log_f32) summed in fp32 within a 256-SNP chunk of the matrix, times ln 2 and summed in float64 across chunks.  The recursion
+ * forgets: the rounding error does not grow with the chain.
+ * Outputs: dosage float [b, n_out, kp] in [0, 2] (pad columns +0.0), call uint8 [b, n_out], post float [b, n_out], ll double
+ * [b, n_seg] (the segment's log-likelihood of the sample's calls).  dosage == NULL runs the forward pass only (n_out may be 0; call,
+ * post, out_snp, oseg and scratch are not touched): the scan over the number of generations.  scratch:
+ * nadm_local_anc_scratch_floats(b, n_out, kp) floats, the checkpoints [n_out][kp (kp + 1) / 2][256 ceil(b / 256)] (0 for a kp without
+ * a kernel); the caller blocks its rows to bound it.  k <= 16 (kp in {4, 8, 12, 16}): the states of a sample live in one thread's
+ * registers; a wider head is refused.  Two launches, one 256-thread block per (256-sample tile, segment), no atomics: a sample's
+ * outputs depend on its own row, q, P, rho and the segment alone -- not on its position in the batch, the other rows or the other
+ * segments -- and the same inputs give the same bits.  Every refusal -- a null pointer, an empty batch, M >= 2^31, ld, k and kp,
+ * q_stride, eps, k > 16, n_seg < 1, n_out < 0, alignment (dosage and scratch 16-byte, ll 8-byte, the others 4-byte), too many blocks
+ * -- is reported before anything is launched.  Asynchronous on `stream`.  Not built: phased input, per-component rates, Viterbi paths. */
+int64_t nadm_local_anc_scratch_floats(int32_t b, int64_t n_out, int32_t kp);
+int nadm_local_anc(const uint8_t* xp, int64_t ld, const int32_t* idx, int32_t b, int64_t M,
+                   const float* P, int32_t k, int32_t kp, const float* Q, int32_t q_stride, float eps,
+                   const float* rho, const int32_t* seg, int32_t n_seg,
+                   const int32_t* out_snp, const int32_t* oseg, int64_t n_out,
+                   float* dosage, uint8_t* call, float* post, double* ll, float* scratch, void* stream);
+
 /* ---- Model-fit check: the pairwise correlation of leave-one-out residuals (evalAdmix, Garcia-Erill & Albrechtsen 2020) -----------
  * Does the model describe these samples, and if not, which ones?  Under a good fit the residuals g - 2 pi of two samples are
  * uncorrelated; where the model is wrong the correlation is positive inside the groups it merged or mis-modelled and negative

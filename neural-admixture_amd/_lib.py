@@ -151,6 +151,8 @@ def _load():
         "nadm_resid_project_t_slices": (i32, [i32, i64]),
         "nadm_resid_project_t_scratch_floats": (i64, [i32, i64, i32, i32]),
         "nadm_resid_project_t": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, vp, i32, f32, f32, vp, i32, i32, vp, vp, vp, vp]),
+        "nadm_local_anc_scratch_floats": (i64, [i32, i64, i32]),
+        "nadm_local_anc": (C.c_int, [vp, i64, vp, i32, i64, vp, i32, i32, vp, i32, f32, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
         "nadm_snp_counts": (C.c_int, [vp, i64, vp, i64, i64, vp, vp]),
         "nadm_ld_band": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp]),
         "nadm_select_snps": (C.c_int, [vp, i64, i64, vp, i64, i32, vp, i64, vp]),

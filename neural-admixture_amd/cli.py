@@ -282,6 +282,30 @@ def parse_date_args(argv):
     return p.parse_args(argv)
 
 
+def parse_local_args(argv):
+    p = argparse.ArgumentParser(prog="neural-admixture local",
+                                description="Local ancestry: the posterior ancestry of every sample along the genome under the linkage "
+                                            "model (one rate, single pulse, unphased), from a run's .P and .Q files and the genetic map of "
+                                            "the .bim.  The model has no LD inside a source: prune first and pass the list with --extract")
+    _add_run_args(p, multi_k=True, out="calls and tables")
+    p.add_argument("--generations", type=str, default="auto", metavar="X|auto",
+                   help="generations since admixture (e.g. from `date`); auto (default): the value that maximises the log-likelihood")
+    p.add_argument("--grid", type=float, default=0.5, help="distance in cM between the points at which the posterior is written (default 0.5)")
+    p.add_argument("--scan_samples", type=int, default=512, help="--generations auto looks at no more than this many samples (default 512)")
+    p.add_argument("--morgans", action="store_true", help="column 3 of the .bim is in Morgans (default: cM)")
+    p.add_argument("--rate", type=float, default=1.0, metavar="CM_PER_MB",
+                   help="where column 3 of the .bim is all zero: this many cM per Mb applied to the base-pair column (default 1.0)")
+    p.add_argument("--dosage", action="store_true", help="also write {out_name}.{K}.lanc.dosage.npy, float32 [N, points, K]")
+    p.add_argument("--pops_path", type=str, default=None, metavar="FILE",
+                   help="one group label per sample of the .fam; with --target, the samples to analyse")
+    p.add_argument("--target", type=str, default=None, metavar="LABEL",
+                   help="analyse the samples whose line of --pops_path is LABEL (default: every sample left after --keep / --remove)")
+    p.add_argument("--warn", type=float, default=4.0,
+                   help="warn of a sample whose mean local share is further from its Q than this many times the other samples' spread "
+                        "(default 4, a convention)")
+    return p.parse_args(argv)
+
+
 def _add_cv_refit(p):
     p.add_argument("--cv_rounds", type=int, default=50, metavar="N",
                    help="round limit of a fold's refit (default 50).  The refit starts from the full-data answer, which has seen the "
@@ -899,6 +923,90 @@ def _date_main(argv):
     log.info("    Weighted LD curves and dates saved.")
 
 
+def _local_main(argv):
+    """``local`` mode: {save_dir}/{name}.{K}.P and .Q for every K asked for + the genotypes and the genetic map of the .bim ->
+    {out_name}.{K}.lanc (the called ancestry pair of every sample at every output point), .lanc.sample (per sample: log-likelihood,
+    mean local share next to Q, switches, mean tract), .lanc.mean (per point: mean share and its deviation) and, with --dosage,
+    .lanc.dosage.npy."""
+    from . import localanc
+    args = parse_local_args(argv)
+    ks = _ks_asked(args)
+    gens = None
+    if args.generations != "auto":
+        try:
+            gens = float(args.generations)
+        except ValueError:
+            gens = float("nan")
+        if not (gens > 0.0 and gens < float("inf")):
+            raise SystemExit("    --generations takes a number > 0 or auto.")
+    if not args.grid > 0.0:
+        raise SystemExit("    --grid must be > 0 (cM).")
+    if not args.rate > 0.0:
+        raise SystemExit("    --rate must be > 0 (cM per Mb).")
+    if args.scan_samples < 1:
+        raise SystemExit("    --scan_samples must be >= 1.")
+    if not args.warn > 0.0:
+        raise SystemExit("    --warn must be > 0.")
+    if max(ks) > localanc.MAX_K:
+        raise SystemExit(f"    {localanc.TOO_WIDE}.")
+    if args.target is not None and args.pops_path is None:
+        raise SystemExit("    --target names a label of --pops_path: give that file.")
+    _need_bed(args.data_path, "local needs the genetic map of a .bim file")
+    labels = None
+    if args.pops_path is not None:
+        if not os.path.isfile(args.pops_path):
+            raise SystemExit(f"    {args.pops_path} not found.")
+        with open(args.pops_path, "r") as fb:
+            labels = [ln.strip() for ln in fb.read().splitlines()]
+    paths = _find_run_heads(args, ks, "local")             # before anything is read
+    _, _, bim, ids, chroms = _bed_ids(args.data_path)      # before the GPU check and before any genotype is read
+    cm_all, bp = read_bim_map(bim)
+    cm, from_rate = genetic_map(cm_all, bp, morgans=args.morgans, rate=args.rate)
+    keep = _extract_keep(args.data_path, args.extract)
+    chrom = chrom_codes(chroms)
+    if keep is not None:                                   # the map follows the kept SNPs
+        cm, chrom, bp = cm[keep], chrom[keep], bp[keep]
+        ids, chroms = [v for v, k in zip(ids, keep) if k], [v for v, k in zip(chroms, keep) if k]
+    try:
+        localanc.output_points(cm, chrom, args.grid)
+    except RuntimeError as e:
+        raise SystemExit(f"    {bim}: {e}.") from None
+    group = None
+    if labels is not None:
+        labels = _filter_lines(labels, _sample_keep(args), args.pops_path)
+        if args.target is not None:
+            group = np.asarray([lb == args.target for lb in labels], dtype=bool)
+            if int(group.sum()) < 1:
+                raise SystemExit(f"    --target {args.target}: no sample of {args.pops_path} carries that label.")
+
+    def check_n(n):
+        if labels is not None and len(labels) != n:
+            raise SystemExit(f"    {args.pops_path} lists {len(labels)} labels, the data holds {n} samples.")
+    data, Ps, Qs = _load_run_heads(args, ks, paths, keep, check_n)
+    if from_rate:
+        log.info(f"    Warning: column 3 of {bim} is all zero; the genetic map is {args.rate:g} cM per Mb of column 4, and every tract "
+                 "length scales with that rate.")
+    if keep is None:
+        log.info("    Warning: the model has no LD inside a source; on SNPs that were not LD-pruned the posterior is over-confident: run "
+                 "prune and pass its list with --extract.")
+    idx = None if group is None else torch.from_numpy(np.nonzero(group)[0].astype(np.int32)).to(data.packed.device)
+    for k, P, Q in zip(ks, Ps, Qs):
+        Qg = Q if group is None else Q[group]
+        try:
+            n = gens
+            if n is None:
+                n, grid, lls = localanc.scan_generations(data.packed, data.M, P, Qg, cm, chrom, idx=idx, scan_samples=args.scan_samples)
+                for g_, l_ in zip(grid, lls):
+                    log.info(f"    K={k}: {g_:9.3f} generations: log-likelihood {l_:.6e}")
+                log.info(f"    K={k}: --generations auto chose {n:.4g}.")
+            res = localanc.local_ancestry(data.packed, data.M, P, Qg, cm, chrom, n, idx=idx, grid=args.grid, dosage=args.dosage)
+        except RuntimeError as e:
+            raise SystemExit(f"    K={k}: {e}.") from None
+        localanc.log_results(res, Qg, cm, k, log, args.warn)
+        localanc.write_results(os.path.dirname(_out_stem(args)), args.out_name or args.name, k, res, Qg, cm, chroms, ids, bp)
+    log.info("    Local ancestry calls and tables saved.")
+
+
 def _king_main(argv):
     """``king`` mode: the genotypes alone -> {name}.king (``i j phi n hethet ibs0`` per pair at or above --cutoff, 0-based indices
     among the samples analysed, by i then j) and {name}.king.in / .king.out, the kept and the removed samples of ``king.unrelated_set`` as ``FID IID``
@@ -1038,14 +1146,14 @@ def _train_worker(rank, args, num_gpus, data, V, pops, t0):
 
 
 _ANALYSIS_MODES = {"king": _king_main, "kinship": _kinship_main, "prune": _prune_main, "hwe": _hwe_main, "cv": _cv_main, "bootstrap": _bootstrap_main,
-                   "pse": _pse_main, "qse": _qse_main, "fit": _fit_main, "pca": _pca_main, "residpca": _residpca_main, "date": _date_main}
+                   "pse": _pse_main, "qse": _qse_main, "fit": _fit_main, "pca": _pca_main, "residpca": _residpca_main, "date": _date_main, "local": _local_main}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "qse", "fit", "pca", "residpca", "date"), \
+    assert argv and argv[0] in ("train", "infer", "king", "kinship", "prune", "hwe", "cv", "bootstrap", "pse", "qse", "fit", "pca", "residpca", "date", "local"), \
         ('Please provide either the argument "train" or "infer" to choose running mode ("king" finds relatives before a run, "kinship", "prune" and "hwe" check a run\'s assumptions, '
-         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "qse" on Q given P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes, "residpca" those of the model\'s residuals, "date" dates the admixture from the decay of weighted LD).')
+         '"cv" helps to choose K, "bootstrap" puts standard errors on Q, "pse" on P, "qse" on Q given P, "fit" checks the fit sample by sample, "pca" gives the principal components of the genotypes, "residpca" those of the model\'s residuals, "date" dates the admixture from the decay of weighted LD, "local" gives the ancestry along each genome).')
     mode, t0 = argv[0], time.time()
     if mode in _ANALYSIS_MODES:                             # (their argument and file checks come before the GPU check)
         _ANALYSIS_MODES[mode](argv[1:])

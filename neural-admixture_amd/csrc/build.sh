@@ -34,6 +34,7 @@ X="$*"
 #   nadm_resid_cor    model-fit check: EM sums and the correlation of leave-one-out residuals (nadm_em_sums, nadm_resid_cor; not on the training path)
 #   nadm_obs_project  standardised PCA: the two observed-calls pair products on the matrix pipe (nadm_obs_project, nadm_obs_project_t; not on the training path)
 #   nadm_resid_project  residual PCA given Q and P: the two products of the standardised residuals (nadm_resid_project, nadm_resid_project_t; not on the training path)
+#   nadm_local_anc    local ancestry: the linkage model's forward-backward recursion along the genome (nadm_local_anc; not on the training path)
 # Host-only units, compiled as plain C++ (no device pass):
 #   nadm_passes_host  the entry points, argument checks and launch rules of the genotype passes and the MLP pair
 #   nadm_gmm          decoder-init mixture fit on the host
@@ -63,6 +64,7 @@ $X $FLAGS -c nadm_sample_info.hip -o $obj/nadm_sample_info.o
 $X $FLAGS -c nadm_resid_cor.hip -o $obj/nadm_resid_cor.o
 $X $FLAGS -c nadm_obs_project.hip -o $obj/nadm_obs_project.o
 $X $FLAGS -c nadm_resid_project.hip -o $obj/nadm_resid_project.o
+$X $FLAGS -c nadm_local_anc.hip -o $obj/nadm_local_anc.o
 $X $HOST -c nadm_passes_host.cpp -o $obj/nadm_passes_host.o
 $X $HOST -c nadm_gmm.cpp -o $obj/nadm_gmm.o
 $X $HOST -c nadm_host_io.cpp -o $obj/nadm_host_io.o
@@ -71,7 +73,7 @@ $X $HOST -c nadm_ld_sweep.cpp -o $obj/nadm_ld_sweep.o
 $X $HOST -c nadm_hooks.cpp -o $obj/nadm_hooks.o
 $X $HOST -DNADM_TEST_HOOKS -c nadm_hooks.cpp -o $obj/nadm_hooks_th.o
 UNITS
-OBJS="nadm_genotype_passes.o nadm_small_kernels.o nadm_step.o nadm_passes_host.o nadm_gmm.o nadm_gmm_dev.o nadm_calib.o nadm_project.o nadm_project_p.o nadm_kinship.o nadm_ibd.o nadm_king.o nadm_ld.o nadm_wld.o nadm_snp_hwe.o nadm_cv.o nadm_snp_info.o nadm_sample_info.o nadm_resid_cor.o nadm_obs_project.o nadm_resid_project.o nadm_host_io.o nadm_layout.o nadm_ld_sweep.o"
+OBJS="nadm_genotype_passes.o nadm_small_kernels.o nadm_step.o nadm_passes_host.o nadm_gmm.o nadm_gmm_dev.o nadm_calib.o nadm_project.o nadm_project_p.o nadm_kinship.o nadm_ibd.o nadm_king.o nadm_ld.o nadm_wld.o nadm_snp_hwe.o nadm_cv.o nadm_snp_info.o nadm_sample_info.o nadm_resid_cor.o nadm_obs_project.o nadm_resid_project.o nadm_local_anc.o nadm_host_io.o nadm_layout.o nadm_ld_sweep.o"
 cd "$obj"
 link="hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-soname,libnadm.so"
 if [ -n "$out" ]; then

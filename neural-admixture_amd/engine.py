@@ -781,6 +781,23 @@ class Engine:
                              maxdist=ad.MAXDIST if maxdist is None else maxdist,
                              min_share=ad.MIN_SHARE if min_share is None else min_share, nmin=nmin)
 
+    def local_ancestry(self, cm, chrom, generations: Optional[float] = None, head: int = 0, idx: Optional[torch.Tensor] = None,
+                       grid: Optional[float] = None, dosage: bool = False):
+        """The posterior local ancestry of one sample group of the resident matrix -- the rows ``idx`` (int32, default: all) -- under
+        the linkage model (localanc.local_ancestry; include/nadm.h, nadm_local_anc) given head ``head``'s P and the encoder's final Q,
+        on the genetic map ``cm [M]`` (cM) and the chromosomes ``chrom [M]``, at output points every ``grid`` cM.  ``generations``
+        None: the value that maximises the log-likelihood (localanc.scan_generations).  A ``LocalAncestry``.  One rate for all
+        components, a single pulse, unphased, no LD inside a source: prune first."""
+        from . import localanc as la
+        self._analysis("local_ancestry", "use localanc.local_ancestry on one GPU from the written .P and .Q files", head=head,
+                       max_k=(la.MAX_K, la.TOO_WIDE))
+        P, Q = self._fitted(head)
+        Qg = Q if idx is None else Q[idx.long()]
+        if generations is None:
+            generations = la.scan_generations(self.xp, self.M, P, Qg, cm, chrom, idx=idx)[0]
+        return la.local_ancestry(self.xp, self.M, P, Qg, cm, chrom, generations, idx=idx, grid=la.GRID if grid is None else grid,
+                                 dosage=dosage)
+
     def read_loss(self, reset: bool = True):
         """(running sum since last reset, last step) -- one host sync."""
         v = self.loss_acc.cpu().numpy().copy()
